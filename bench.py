@@ -11,7 +11,7 @@ metric "2048-bit modexps/sec (encrypt+decrypt)" is quoted on; it mirrors the ref
 BM_Decrypt (benchmark/bench_cryptography.cpp:73-121: same key, same HS_BN, DJN on).
 
 How N GPUs are driven:
-  * `python bench.py --gpus N` (plain): ONE process, the library's device pool (pgpu_init_all: one worker pair +
+  * `python bench.py --gpus N` (direct, no torchrun): ONE process, the library's device pool (pgpu_init_all: one worker pair +
     streams per GPU, key images replicated by one RCCL broadcast over xGMI); the global batch of N x 8192
     elements is a sharded resident pgpu_batch, a step enqueues one launch per GPU.  This is also the N = 1 path.
   * under torch.distributed.run (WORLD_SIZE set): one process per GPU, backend nccl == RCCL; every rank
@@ -20,8 +20,16 @@ How N GPUs are driven:
 Both are weak scaling (8192 elements per GPU per step); timing = barrier/synchronise on both sides of exactly K
 steps, MAX over ranks.  Consecutive steps rotate over the library's four batch lanes (--in-flight, default 4 since round 5:
 four independent batches of 8192 in flight per GPU, each lane's launches on a quarter of the chip -- csrc/policy.cpp); every
-step is a whole encrypt + decrypt of one batch, and every lane's results are checked after the timed region.  `--config 4|5` runs BASELINE.json configs[3] / configs[4] instead: a FIXED total batch
-(65536 x 3072-bit encrypt+decrypt; 1 M x 2048-bit CT+CT and CT x PT) sharded over the N GPUs (strong scaling).
+step is a whole encrypt + decrypt of one batch (with --full, every lane's results are checked after the timed region).
+`--config 4|5` runs BASELINE.json configs[3] / configs[4] instead: a FIXED total batch (65536 x 3072-bit
+encrypt+decrypt; 1 M x 2048-bit CT+CT and CT x PT) sharded over the N GPUs (strong scaling).
+
+The headline (the default --config 2, direct or under torchrun) is lean unless --full is given: the run sets up, warms
+up, times exactly --steps steps and prints the contract line (metric, value, ms_per_step, ...; the roofline block stays
+null).  `--full` adds everything else behind the timed region: per-kernel times and the roofline, the sustained and
+hardened runs, the round trip and oracle checks (all-reduced over the ranks under torchrun), the N = 1 extras and the
+CPU baseline.  `--config 4|5` ignore --full: they always run their checks and side measurements and fill the roofline.
+`--dump-outputs DIR` writes what the timed path computed in its last step (bench.py: dump_outputs).
 """
 import argparse
 import ctypes
@@ -78,6 +86,30 @@ def synth(rank, count, nw, pw):
     return m, r
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: {name: uint64 limb array (rows, words)} -> out_dir/<name>.npy as float64 arrays of 32-bit limbs
+    (rows, 2 * words), least significant limb first -- every value exact.  Outputs larger than DUMP_LIMIT_BYTES in all
+    keep a fixed, seeded sample of rows (the same rows of every array, written as row_index.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows = {a.shape[0] for a in arrays.values()}
+    if len(rows) != 1:
+        raise ValueError(f"dump_outputs: arrays with different row counts {sorted(rows)}")
+    nrows = rows.pop()
+    row_bytes = sum(a.shape[1] * 2 * 8 for a in arrays.values())
+    idx = None
+    if nrows * row_bytes > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // row_bytes
+        idx = np.sort(np.random.default_rng(seed).choice(nrows, size=keep, replace=False))
+        np.save(os.path.join(out_dir, "row_index.npy"), idx.astype(np.float64))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a if idx is None else a[idx], dtype=np.uint64)
+        limbs32 = np.stack([a & np.uint64(0xFFFFFFFF), a >> np.uint64(32)], axis=-1).reshape(a.shape[0], 2 * a.shape[1])
+        np.save(os.path.join(out_dir, name + ".npy"), limbs32.astype(np.float64))
+
+
 def collect_timing(L, cap):
     kinds = (ctypes.c_int * cap)()
     kms = (ctypes.c_double * cap)()
@@ -129,12 +161,23 @@ def main():
                          "runs the one-lane product-scanning kernel, 256 wavefronts on 64 CUs, the encrypt two workgroups per "
                          "CU on the same quarter; 2: each lane owns half the chip with the sequential-halves kernels, the "
                          "round-4 headline: batches_in_flight_sweep in the line has every k)")
+    ap.add_argument("--full", action="store_true",
+                    help="(--config 2, the headline) after the timed region, also run every side measurement and check: "
+                         "per-kernel times and the roofline block, the sustained-rate and hardened runs, the round trip and "
+                         "oracle checks, the N=1 extras and the CPU baseline.  Without it the headline run sets up, warms up, "
+                         "times --steps steps and prints the line.  --config 4|5 always run their checks and side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float64 arrays of "
+                         "32-bit limbs, least significant first: exact; a fixed, seeded sample of rows if the whole "
+                         "output exceeds 64 MB)")
     ap.add_argument("--sustain-seconds", type=float, default=2.0,
-                    help="length of the sustained-rate run behind the timed region (N = 1; 0 skips it)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="length of the sustained-rate run behind the timed region (N = 1, --full; 0 skips it)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the N=1 side measurements (end-to-end, API level, non-DJN variant)")
+                    help="(--full) skip the N=1 side measurements (end-to-end, API level, non-DJN variant)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
         if args.gpus != world:
@@ -230,6 +273,28 @@ def run_pool(args):
     elapsed = time.perf_counter() - t0
     timed_trace = collect_trace(L, 8 * args.steps + 64)
     timed_forms = [(k, f, ms) for k, f, ms, _, _ in timed_trace]
+    parallelism = f"in-process device pool x{N} (batch sharded; key images: {L.pgpu_pool_transport().decode()})"
+    if args.dump_outputs:                   # the last timed step's results, before anything else reuses its lane
+        last = (state["i"] - 1) % nfl
+        dump_outputs(args.dump_outputs, {"ciphertext": B.down(state["c"][last]), "plaintext": B.down(state["out"][last])})
+    if not args.full:
+        _capi.check(L.pgpu_set_timing(0))
+        result = headline_fields(args, N, elapsed, parallelism)
+        result["config"]["batches_in_flight_per_gpu"] = nfl
+        result["config"]["lane_priming_steps"] = priming
+        result["config"]["secret_table_access"] = "masked" if L.pgpu_get_table_gather_policy() else "indexed"
+        if nfl > 1:
+            result["config"]["workload"] += ("; %d batches in flight per GPU: consecutive steps rotate over %d of the library's "
+                                             "batch lanes (streams), exactly K steps timed" % (nfl, nfl))
+        result["kernel_forms_in_timed_region"] = forms_summary(timed_forms)
+        result["host_issue_ms_per_step"] = round(t_issue / args.steps * 1e3, 4)
+        result["full"] = "not run: per-kernel times, roofline, side measurements, checks and CPU baseline come with --full"
+        B.free(*[h for pair in sets for h in pair], *state["c"], *state["out"])
+        del pk, sk
+        pa.terminate()
+        ctypes.CDLL(None).fflush(None)
+        bench_line.emit(result)
+        return
     single_ms = None
     if nfl == 1:
         per_kind = forms_to_kinds(timed_forms)
@@ -318,8 +383,7 @@ def run_pool(args):
     per_gpu = per_gpu_report(L, N, per_kind)
 
     fb = fixed_base_info(L, pk)
-    result = headline(args, N, elapsed, per_kind, nw, pw,
-                      f"in-process device pool x{N} (batch sharded; key images: {L.pgpu_pool_transport().decode()})",
+    result = headline(args, N, elapsed, per_kind, nw, pw, parallelism,
                       decrypt_kernel(sk, BATCH, nw, KEY_BITS),
                       encrypt_kernel(pk, BATCH, nw, KEY_BITS, fb["window"] or int(os.environ.get("PGPU_FB_WINDOW", "13"))), fb)
     result["config"]["secret_exponent_policy"] = ["fixed-window", "sliding"][L.pgpu_get_secret_exponent_policy()]
@@ -731,6 +795,31 @@ def encrypt_kernel(pk, count, nw, key_bits, fbw, busy_lanes=0):
             "full-width products back to c*R mod n^2" % (fbw, nprod))
 
 
+def headline_fields(args, world, elapsed, parallelism):
+    """the headline figure and its configuration: everything of the contract line that the timed region alone gives"""
+    return {
+        "metric": "2048-bit modexps/sec (encrypt+decrypt)",
+        "value": round(3 * BATCH * world * args.steps / elapsed, 1),
+        "unit": "modexps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u64",
+        "data": "synthetic",
+        "config": {
+            "workload": "k=2048 ISO/IEC 18033-6 key, DJN: encrypt batch=8192 (mod n^2, 4096 b, e=1024 b) "
+                        "+ CRT decrypt batch=8192 (2x mod p^2/q^2, 2048 b, e=1024 b) per GPU per step",
+            "batch_per_gpu": BATCH, "modexps_per_step_per_gpu": 3 * BATCH,
+            "parallelism": parallelism,
+            "elements_per_s": round(BATCH * world * args.steps / elapsed, 1),
+        },
+    }
+
+
 def headline(args, world, elapsed, per_kind, nw, pw, parallelism, dec_kernel=None, enc_kernel=None, fb=None):
     """the contract line (metric / value / roofline of the dominant kernel) from the timed region's numbers"""
     fixed_base = K_FB in per_kind
@@ -741,8 +830,6 @@ def headline(args, world, elapsed, per_kind, nw, pw, parallelism, dec_kernel=Non
         modexp_ms = modexp_ms[1::2]
     dec_ms = float(np.mean(modexp_ms))
     crt_ms = float(np.mean(per_kind[K_CRT]))
-    modexps_per_step = 3 * BATCH * world
-    value = modexps_per_step * args.steps / elapsed
     mac_enc = algorithmic_mac32(2 * KEY_BITS, KEY_BITS // 2) * BATCH        # 41.48 M * 8192
     mac_dec = 2 * algorithmic_mac32(KEY_BITS, KEY_BITS // 2) * BATCH        # 20.82 M * 8192
     alg_bytes_dec = (2 * nw * 8 + nw * 8) * BATCH                           # c + m = 768 B/elt
@@ -777,25 +864,7 @@ def headline(args, world, elapsed, per_kind, nw, pw, parallelism, dec_kernel=Non
         enc_name = f"modexp_kernel<{geo_name(2 * nw, 2 * KEY_BITS, BATCH)}> (encrypt)"
         enc_note = "generic square-and-multiply"
     return {
-        "metric": "2048-bit modexps/sec (encrypt+decrypt)",
-        "value": round(value, 1),
-        "unit": "modexps/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u64",
-        "data": "synthetic",
-        "config": {
-            "workload": "k=2048 ISO/IEC 18033-6 key, DJN: encrypt batch=8192 (mod n^2, 4096 b, e=1024 b) "
-                        "+ CRT decrypt batch=8192 (2x mod p^2/q^2, 2048 b, e=1024 b) per GPU per step",
-            "batch_per_gpu": BATCH, "modexps_per_step_per_gpu": 3 * BATCH,
-            "parallelism": parallelism,
-            "elements_per_s": round(BATCH * world * args.steps / elapsed, 1),
-        },
+        **headline_fields(args, world, elapsed, parallelism),
         "roofline": {
             "bound": "int-alu",
             "bound_note": "VALU issue rate: v_mad_u64_u32 issues at full rate, one wave64 instruction per 4 cycles per SIMD "
@@ -1486,6 +1555,8 @@ def run_config45(args, pa, L, B, N):
         elapsed = time.perf_counter() - t0
         per = collect_timing(L, 4 * args.steps + 8)
         _capi.check(L.pgpu_set_timing(0))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"ciphertext": B.down(st["c"]), "plaintext": B.down(st["o"])})
         assert np.array_equal(B.down(st["o"]), m_host), "config 4: round trip failed"
         opk = orc.PublicKey(n, bits)
         opk.set_djn(hs)
@@ -1597,6 +1668,8 @@ def run_config45(args, pa, L, B, N):
     t_mul = (time.perf_counter() - t0) / max(1, args.steps // 4)
     per_mul = collect_timing(L, args.steps + 8)
     _capi.check(L.pgpu_set_timing(0))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"ct_add": B.down(st["s"]), "ct_mul_pt": B.down(st["t"])})
     idx = [0, 1, total // 2, total - 1]
     av, bv, ev = limbs_to_ints(a_host[idx]), limbs_to_ints(b_host[idx]), [int(x) for x in e_host[idx, 0]]
     assert limbs_to_ints(B.down(st["s"])[idx]) == [x * y % nsq for x, y in zip(av, bv)], "config 5: CT+CT differs"
@@ -1750,6 +1823,26 @@ def run_ranks(args, world):
         step()
     sync_all()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:     # rank 0's shard of the last timed step
+        last = (state["i"] - 1) % nfl
+        dump_outputs(args.dump_outputs, {"ciphertext": B.down(state["c"][last]), "plaintext": B.down(state["out"][last])})
+    if not args.full:
+        _capi.check(L.pgpu_set_timing(0))
+        collect_timing(L, 4 * args.steps + 8)
+        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        if rank == 0:
+            result = headline_fields(args, world, float(t.item()),
+                                     f"one process per GPU x{world} (torch.distributed {backend}; key broadcast only)")
+            result["config"]["batches_in_flight_per_gpu"] = nfl
+            result["config"]["secret_table_access"] = "masked" if L.pgpu_get_table_gather_policy() else "indexed"
+            result["full"] = "not run: per-kernel times, roofline and checks come with --full"
+            bench_line.emit(result)
+        B.free(*state["c"], *state["out"], *[h for pair in sets for h in pair])
+        dist.barrier()
+        dist.destroy_process_group()
+        pa.terminate()
+        return
     if nfl == 1:
         per_kind = collect_timing(L, 4 * args.steps + 8)
     else:                       # per-kernel times from a short pass on ONE lane (launches do not overlap in it)

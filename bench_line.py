@@ -63,8 +63,8 @@ def compact(detail):
     roof = {k: _num(r.get(k)) for k in ROOFLINE_KEYS}
     if roof.get("kernel") is not None:
         roof["kernel"] = _clip(roof["kernel"], 200)
-    if roof.get("chip_share") is None:
-        roof["chip_share"] = 1.0            # a launch that has the chip to itself
+    if roof.get("chip_share") is None and r:
+        roof["chip_share"] = 1.0            # a launch that has the chip to itself (a plain run has no roofline: all null)
     out["roofline"] = roof
     cb = detail.get("cpu_baseline")
     if isinstance(cb, dict):

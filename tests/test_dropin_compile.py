@@ -2,33 +2,39 @@
 example/*.cpp -- parse and type-check UNCHANGED against include/ipcl (our mirror of the public ipcl:: API:
 KeyPair / PublicKey / PrivateKey / PlainText / CipherText / BigNumber, ipcl/include/ipcl/*.hpp).
 
-Build container only: the files are compiled where they lie under /root/reference (never copied into this repository);
-googletest / google-benchmark are replaced by the two stand-in headers under tests/cpp/shims (syntax only).  Skips when
-the reference tree is absent (the GPU box)."""
-import glob
+The sources are never copied into this repository: build() compiles them where they lie in the reference tree
+(oracle/ref_dropin.py; googletest / google-benchmark replaced by the two stand-in headers under tests/cpp/shims) and
+records the outcome in oracle/_ref/dropin.json.  This test reads that record only; the cases are the committed list of
+names in tests/golden/dropin_sources.json.  Skips when build() had no reference tree to compile from."""
+import json
 import os
-import shutil
-import subprocess
 
 import pytest
 
+from oracle import ref_dropin
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-SOURCES = sorted(glob.glob(os.path.join(REF, "test", "*.cpp")) + glob.glob(os.path.join(REF, "benchmark", "*.cpp"))
-                 + glob.glob(os.path.join(REF, "example", "*.cpp")))
+SOURCES = json.load(open(os.path.join(ROOT, "tests", "golden", "dropin_sources.json")))["sources"]
 
 
-@pytest.mark.skipif(not SOURCES, reason="reference tree not present (it never travels to the GPU box)")
-@pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
-@pytest.mark.parametrize("src", SOURCES or ["-"], ids=lambda s: os.path.relpath(s, REF) if s != "-" else s)
+def _record():
+    if not os.path.exists(ref_dropin.RECORD):
+        pytest.skip("no oracle/_ref/dropin.json: build() had no reference tree to compile the client sources from")
+    with open(ref_dropin.RECORD) as f:
+        rec = json.load(f)
+    assert rec["headers_sha256"] == ref_dropin.header_digest(), \
+        "oracle/_ref/dropin.json was made against other headers than include/ipcl as it stands: run build()"
+    return rec
+
+
+@pytest.mark.parametrize("src", SOURCES)
 def test_reference_client_source_compiles_unchanged(src):
-    cmd = ["g++", "-std=c++17", "-fopenmp", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"),
-           "-I" + os.path.join(ROOT, "tests", "cpp", "shims"), src]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, "%s does not compile against include/ipcl:\n%s" % (os.path.relpath(src, REF), r.stderr[-3000:])
+    r = _record()["results"].get(src)
+    assert r is not None, "%s is not among the client sources build() compiled" % src
+    assert r["returncode"] == 0, "%s does not compile against include/ipcl:\n%s" % (src, r["stderr"])
 
 
 def test_the_check_covers_every_client_source():
-    if not SOURCES:
-        pytest.skip("reference tree not present")
+    rec = _record()
     assert len(SOURCES) >= 11, SOURCES
+    assert rec["found"] == SOURCES, "the reference's client sources and tests/golden/dropin_sources.json differ"

@@ -3,7 +3,7 @@
 # `bench.py --sustain-seconds 20`; then the same for the round-4 mode (--in-flight 2) and for a lone caller (--in-flight 1).
 for nfl in 4 2 1; do
   echo "== bench.py --in-flight $nfl --sustain-seconds 20"
-  python bench.py --in-flight $nfl --no-extras --no-cpu-baseline --sustain-seconds 20 > /tmp/pp_$nfl.json 2>/dev/null &
+  python bench.py --full --in-flight $nfl --no-extras --no-cpu-baseline --sustain-seconds 20 > /tmp/pp_$nfl.json 2>/dev/null &
   BP=$!
   sleep 9
   for i in 1 2 3 4 5 6 7 8; do

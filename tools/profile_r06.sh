@@ -7,7 +7,7 @@
 set -x
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
-B="--no-cpu-baseline --no-extras --sustain-seconds 0"
+B="--full --no-cpu-baseline --no-extras --sustain-seconds 0"
 RUNS=${RUNS:-"f4 f1 c4 c5"}
 for run in $RUNS; do
   OUT=$REPO/gpurun_out/prof_r06$run
@@ -29,7 +29,7 @@ cd $REPO
 OUT=$REPO/gpurun_out/r06p
 mkdir -p $OUT
 if [ "${EXTRA:-1}" = 0 ]; then exit 0; fi
-line() { python bench.py "${@:2}" > $OUT/$1.line.json 2> $OUT/$1.err; cp gpurun_out/bench_detail.json $OUT/$1.json; }
+line() { python bench.py --full "${@:2}" > $OUT/$1.line.json 2> $OUT/$1.err; cp bench_detail.json $OUT/$1.json; }
 line bench_n1 --steps 20 --warmup 5
 line bench_f1 --in-flight 1 --steps 20 --warmup 3 --no-cpu-baseline --no-extras
 line bench_f2 --in-flight 2 --steps 20 --warmup 3 --no-cpu-baseline --no-extras
