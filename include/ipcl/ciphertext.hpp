@@ -11,6 +11,11 @@
 
 namespace ipcl {
 
+class CipherText;
+namespace ext {   // include/ipcl/ext/linear.hpp
+CipherText matVec(const PlainText& w, std::size_t rows, const CipherText& x);
+}
+
 class CipherText : public BaseText {
  public:
   CipherText() = default;
@@ -35,6 +40,8 @@ class CipherText : public BaseText {
 
  private:
   friend class PublicKey;
+  friend CipherText ext::matVec(const PlainText& w, std::size_t rows, const CipherText& x);
+  CipherText linearMap(const PlainText& w, std::size_t rows) const;   // prod_j this[j]^w[i][j]: csrc/host/linear.cpp
   CipherText(const PublicKey& pk, std::shared_ptr<detail::DeviceBatch> dev);
   CipherText(std::shared_ptr<PublicKey> pk, std::shared_ptr<detail::DeviceBatch> dev);
   std::shared_ptr<PublicKey> m_pk;

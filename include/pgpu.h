@@ -300,6 +300,27 @@ int pgpu_batch_ct_add_plain(const pgpu_pubkey* key, const pgpu_batch* a, const p
 /* out = a^e mod n^2 (CipherText * PlainText, ciphertext.cpp:83-106); e may hold one element */
 int pgpu_batch_ct_mul(const pgpu_pubkey* key, const pgpu_batch* a, const pgpu_batch* e, int e_bits,
                       pgpu_batch** out);
+/* Encrypted matrix-vector product (an encrypted linear layer, a weighted aggregate, a dot product): x a resident
+ * ciphertext batch of cols = pgpu_batch_count(x) elements (pair rows, or uploaded plain ciphertext words: converted on
+ * the way in), w a plain uploaded batch of rows*cols exponents, row-major, each < 2^e_bits (bits at and above e_bits are
+ * ignored):
+ *     out[i] = prod_j x[j]^w[i*cols + j] mod n^2           i.e. Dec(out[i]) = sum_j w[i][j] * Dec(x[j]) mod n
+ * One simultaneous fixed-window multi-exponentiation instead of rows*cols pgpu_batch_ct_mul terms and a tree of
+ * pgpu_batch_ct_add: the window tables of the x[j] are built once and shared by all rows, the e_bits squarings are done
+ * once per output ("Encrypted matrix-vector product").  The result is an ordinary resident ciphertext batch of
+ * `rows` elements on the lane of x.
+ * PGPU_ERR_INVALID_PARAM: null / stale handles, rows == 0, count(w) != rows*cols, e_bits < 1 or wider than the rows of w.
+ * PGPU_ERR_UNSUPPORTED: keys without pair rows (beyond 3072 bits; PGPU_PAIR_ROWS=0 / PGPU_HENSEL=0), pools of more than one
+ * GPU, and -- SIDE CHANNELS -- the masked table-gather policy: the tables are indexed by digits of the PLAINTEXT matrix w
+ * (never by key material or by anything encrypted), which is the indexed access of the default policy; with
+ * pgpu_set_table_gather_policy(1) the call is refused rather than run with an access pattern the policy excludes. */
+int pgpu_batch_ct_matvec(const pgpu_pubkey* key, const pgpu_batch* x, const pgpu_batch* w, size_t rows, int e_bits,
+                         pgpu_batch** out);
+/* What a call of this shape would run (host-side query, needs no device): the window width (1..6), the number of column
+ * slices (1..cols; each slice of a row is one group of lanes and runs its own squarings, the partial products are folded
+ * afterwards) and the bytes of the shared window table (cols * 2^window pair rows).  The rule is policy.hpp: matvec_*;
+ * PGPU_MATVEC_WINDOW / PGPU_MATVEC_SLICES force the two values.  PGPU_ERR_UNSUPPORTED: no pair rows for keys of key_bits. */
+int pgpu_ct_matvec_plan(int key_bits, size_t rows, size_t cols, int e_bits, int* window, int* slices, size_t* table_bytes);
 
 /* ---- instrumentation used by bench.py (roofline) ----
  * With timing enabled every kernel launch is bracketed by two HIP events recorded on the stream
@@ -310,7 +331,8 @@ typedef enum pgpu_kernel_kind {
   PGPU_KERNEL_MODEXP = 1,     /* modexp_kernel (generic / encrypt / decrypt stage 1) */
   PGPU_KERNEL_MODMUL = 2,     /* modmul_kernel */
   PGPU_KERNEL_CRT = 3,        /* crt_kernel (decrypt stage 2) */
-  PGPU_KERNEL_FB_ENCRYPT = 4  /* fb_encrypt_kernel (DJN encrypt, fixed-base) */
+  PGPU_KERNEL_FB_ENCRYPT = 4, /* fb_encrypt_kernel (DJN encrypt, fixed-base) */
+  PGPU_KERNEL_MATVEC = 5      /* every launch of pgpu_batch_ct_matvec: table build, multi-exponentiation, fold */
 } pgpu_kernel_kind;
 int pgpu_set_timing(int enabled);
 int pgpu_timing_collect(int* kinds, double* ms, int max_entries);

@@ -35,6 +35,7 @@ SYMBOLS = [
     "pgpu_build_features", "pgpu_batch_is_current", "pgpu_batch_lanes", "pgpu_timing_collect_ex", "pgpu_decrypt_kernel_form_ex",
     "pgpu_encrypt_kernel_form_ex", "pgpu_host_alloc", "pgpu_host_free", "pgpu_host_wait",
     "pgpu_timing_collect_trace",
+    "pgpu_batch_ct_matvec", "pgpu_ct_matvec_plan",
 ]
 FEATURE_4096_SPLIT = 1
 
@@ -164,6 +165,10 @@ def lib():
     L.pgpu_decrypt_kernel_form_ex.restype = c_int
     L.pgpu_encrypt_kernel_form_ex.argtypes = [c_void_p, c_int, c_size_t, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]
     L.pgpu_encrypt_kernel_form_ex.restype = c_int
+    L.pgpu_batch_ct_matvec.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_int, POINTER(c_void_p)]
+    L.pgpu_batch_ct_matvec.restype = c_int
+    L.pgpu_ct_matvec_plan.argtypes = [c_int, c_size_t, c_size_t, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_size_t)]
+    L.pgpu_ct_matvec_plan.restype = c_int
     _lib = L
     return L
 

@@ -50,7 +50,7 @@ def hensel_parts():
     skip = {15, 30}      # (retired in round 6: the A/B-wavefront experiment and the operand-scanning one-lane kernel)
     if not build_4096():
         skip |= {22, 23, 24}
-    return [p for p in range(38) if p not in skip]
+    return [p for p in range(41) if p not in skip]
 
 
 def _objects():
@@ -82,6 +82,8 @@ def _objects():
             hdeps_k.append(os.path.join(CSRC, "hensel_wave.hpp"))
         if part in (36, 37):
             hdeps_k.append(os.path.join(CSRC, "hensel_wave_n2.hpp"))
+        if part in (38, 39, 40):
+            hdeps_k.append(os.path.join(CSRC, "hensel_matvec.hpp"))
         out.append((o, hip + [f"-DPGPU_PART={part}", "-c", src, "-o", o], [src] + hdeps_k + kdeps))
     for name in ("capi.cpp", "policy.cpp", "runtime.cpp", os.path.join("host", "bignum.cpp")):
         src = os.path.join(CSRC, name)
@@ -174,6 +176,7 @@ def build_pgpu(force=False):
     if todo or relink or not os.path.exists(out):
         _run([hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC"] + [o for o, _, _ in objs]
              + ["-ldl", "-lpthread", "-o", out])
+    build_dropin()      # (include/pgpu.h is among the headers the record is made against)
     return out
 
 
@@ -190,6 +193,7 @@ def build_ipcl(force=False):
     if force or _newer(out, cpps + hdrs):
         _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fopenmp", "-I" + os.path.join(ROOT, "include")]
              + cpps + ["-L" + HERE, "-lpgpu", "-Wl,-rpath,$ORIGIN", "-o", out])
+    build_dropin()
     return out
 
 
@@ -227,8 +231,21 @@ def build_oracle(force=False):
     return out
 
 
+def build_dropin():
+    """The drop-in record of the public headers (oracle/ref_dropin.py: the reference's own client sources compiled
+    against include/).  It names the headers it was made against, so it is a product of include/ like the libraries are:
+    every entry point that brings the libraries up to date brings the record up to date too -- a tree whose headers
+    changed under an existing record (another commit checked out over a built one) is then never left with a stale one.
+    A no-op while the record matches the headers, and where there is no reference tree to compile from."""
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    from oracle import ref_dropin
+    return ref_dropin.build()
+
+
 def build_all(force=False):
     build_pgpu(force)
     build_ipcl(force)
     build_api_bench(force)
     build_oracle(force)
+    build_dropin()

@@ -573,6 +573,115 @@ int pgpu_batch_ct_mul(const pgpu_pubkey* key, const pgpu_batch* a, const pgpu_ba
   return PGPU_OK;
 }
 
+// ---- encrypted matrix-vector product (hensel_matvec.hpp; policy.hpp: matvec_*) ----
+int pgpu_ct_matvec_plan(int key_bits, size_t rows, size_t cols, int e_bits, int* window, int* slices, size_t* table_bytes) {
+  if (key_bits < 1 || rows == 0 || cols == 0 || e_bits < 1)
+    return fail(PGPU_ERR_INVALID_PARAM, "matvec plan: key_bits, rows, cols and e_bits must be positive");
+  int G = 0, K = 0;
+  if (!policy::matvec_geometry(key_bits, &G, &K))
+    return fail(PGPU_ERR_UNSUPPORTED, "matvec: keys of this size have no pair rows (1024- to 3072-bit key classes only)");
+  const size_t row_bytes = (size_t)2 * G * K * sizeof(uint32_t);
+  const size_t S = policy::matvec_slices(G, rows, cols);
+  const int w = policy::matvec_window(rows, cols, e_bits, S, row_bytes);
+  if (window) *window = w;
+  if (slices) *slices = (int)S;
+  if (table_bytes) *table_bytes = cols * ((size_t)1 << w) * row_bytes;
+  return PGPU_OK;
+}
+
+int pgpu_batch_ct_matvec(const pgpu_pubkey* key, const pgpu_batch* x, const pgpu_batch* w, size_t rows, int e_bits,
+                         pgpu_batch** out) {
+  RC_TRY(rt::check_ready());
+  if (!key || !x || !w || !out) return fail(PGPU_ERR_INVALID_PARAM, "null argument");
+  RC_TRY(check_gen(key->gen, "key"));
+  RC_TRY(check_gen(x->gen, "batch"));
+  RC_TRY(check_gen(w->gen, "batch"));
+  const int W = 2 * key->n_words;
+  const size_t cols = x->count;
+  if (rows == 0) return fail(PGPU_ERR_INVALID_PARAM, "matvec error: rows must be positive");
+  if (x->words != W) return fail(PGPU_ERR_INVALID_PARAM, "matvec error: ciphertext width mismatch");
+  if (w->mont || w->pair_l2) return fail(PGPU_ERR_INVALID_PARAM, "matvec error: the matrix must be a plain uploaded batch");
+  if (rows > ~(size_t)0 / cols || w->count != rows * cols)
+    return fail(PGPU_ERR_INVALID_PARAM, "matvec error: Size mismatch! (the matrix must hold rows * count(x) values)");
+  if (e_bits < 1 || e_bits > 64 * w->words) return fail(PGPU_ERR_INVALID_PARAM, "matvec error: e_bits outside the rows of the matrix batch");
+  if (!same_domain(x->mont, key->nsq)) return fail(PGPU_ERR_INVALID_PARAM, "matvec error: batch belongs to a different key");
+  if (rt::pool_size() > 1)
+    return fail(PGPU_ERR_UNSUPPORTED, "matvec: pools of more than one GPU are not supported (rows are not sharded yet)");
+  const pgpu_pubkey::PubForm* pf = pair_form(key);
+  if (!pf || !pgpu::matvec_has(pf->H, pf->K))
+    return fail(PGPU_ERR_UNSUPPORTED, "matvec: key has no pair form (1024- to 3072-bit keys; PGPU_PAIR_ROWS=0 / PGPU_HENSEL=0 switch it off)");
+  // the window tables are addressed by digits of the caller's plaintext matrix: indexed access.  Under the masked
+  // policy the call is refused rather than quietly breaking that promise.
+  if (g_ct_gather.load())
+    return fail(PGPU_ERR_UNSUPPORTED, "matvec: the masked table-gather policy is on (pgpu_set_table_gather_policy / PGPU_CT_GATHER) and "
+                                      "this call indexes its window tables by digits of the plaintext matrix; no masked variant exists");
+  std::unique_ptr<pgpu_batch> tx;
+  RC_TRY(as_pair_batch(key, x, &x, &tx));
+  const int G = pf->H, K = pf->K, l2 = G * K;
+  const size_t LQ = (size_t)2 * l2, row_bytes = LQ * sizeof(uint32_t);
+  const size_t S = policy::matvec_slices(G, rows, cols);
+  const int win = policy::matvec_window(rows, cols, e_bits, S, row_bytes);
+  std::unique_ptr<pgpu_batch> o;
+  RC_TRY(new_batch(rows, W, &o, l2, x->lane));
+  o->pair_form = pair_form_shared(key);
+  rt::Device& dev = rt::device(0);
+  rt::DeviceGuard g(dev.ordinal);
+  hipStream_t s = dev.bs(x->lane);
+  RC_TRY(lanes_order(w, x->lane, true));
+  // table and partial products: the block arena, on the lane's stream like the operands themselves
+  rt::DevMem table, partial;
+  RC_TRY(table.alloc(dev, s, cols * ((size_t)1 << win) * row_bytes));
+  if (S > 1) RC_TRY(partial.alloc(dev, s, S * rows * row_bytes));
+  pgpu::MatvecArgs a{};
+  a.ctx = hensel_pub_view(pf, dev.index);
+  a.x = x->prow(0);
+  a.table = (uint32_t*)table.p;
+  a.w = w->ptr(0);
+  a.w_stride = (size_t)w->words;
+  a.w_words = w->words;
+  a.e_bits = e_bits;
+  a.window = win;
+  a.slices = (int)S;
+  a.rows = rows;
+  a.cols = cols;
+  a.out = S > 1 ? (uint32_t*)partial.p : o->prow(0);
+  const size_t ipw = 64 / (size_t)G;
+  auto blocks_of = [](size_t waves) { return (unsigned)((waves + pgpu::kWavesPerWG - 1) / pgpu::kWavesPerWG); };
+  {
+    TimerScope t(dev, s, PGPU_KERNEL_MATVEC, PGPU_FORM_SEQ);
+    if (!pgpu::launch_matvec_table(G, K, a, blocks_of((cols + ipw - 1) / ipw), s))
+      return fail(PGPU_ERR_UNSUPPORTED, "matvec kernels not compiled for this key class");
+    HIP_TRY(hipGetLastError());
+    t.stop();
+  }
+  {
+    TimerScope t(dev, s, PGPU_KERNEL_MATVEC, PGPU_FORM_SEQ);
+    if (!pgpu::launch_matvec(G, K, a, blocks_of(S * ((rows + ipw - 1) / ipw)), s))
+      return fail(PGPU_ERR_UNSUPPORTED, "matvec kernels not compiled for this key class");
+    HIP_TRY(hipGetLastError());
+    t.stop();
+  }
+  // fold the S partial products of every row: ceil(log2 S) element-wise pair products over the slices, in place (slice h + k
+  // into slice k; a group reads its two rows before it writes one), the last one into the result batch
+  for (size_t cur = S; cur > 1;) {
+    const size_t h = (cur + 1) / 2;
+    pgpu::PairOpsArgs pa{};
+    pa.count = (cur - h) * rows;
+    const pgpu_pubkey::PubForm* lf = pair_op_form(key, pf, pa.count);
+    pa.ctx = hensel_pub_view(lf, dev.index);
+    pa.op = pgpu::PO_MUL;
+    pa.a = (const uint32_t*)partial.p;
+    pa.b = (const uint32_t*)partial.p + h * rows * LQ;
+    pa.b_stride = LQ;
+    pa.out = h == 1 ? o->prow(0) : (uint32_t*)partial.p;
+    RC_TRY(pair_op_launch(dev, lf, pa, s, PGPU_KERNEL_MATVEC));
+    cur = h;
+  }
+  RC_TRY(lanes_order(w, x->lane, false));
+  *out = o.release();
+  return PGPU_OK;
+}
+
 int pgpu_set_batch_lane(int lane) {
   if (lane < 0 || lane >= rt::kBatchLanes) return fail(PGPU_ERR_INVALID_PARAM, "batch lane out of range (pgpu_batch_lanes())");
   t_batch_lane = lane;

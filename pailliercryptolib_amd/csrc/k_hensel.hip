@@ -1,5 +1,5 @@
 // pailliercryptolib_amd -- instantiations of the split-form CRT-decrypt exponentiation (hensel.hpp), split over
-// PGPU_PART = 0..13 so that they compile in parallel (3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
+// PGPU_PART = 0..40 so that they compile in parallel (38-40: the encrypted matrix-vector product; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
 // the two-wavefronts-per-SIMD build of the (2,19) decrypt form; 11-13: element-wise operations on pair rows).
 #include "hensel_seq.hpp"
 #include "launch.hpp"
@@ -12,9 +12,12 @@
 #if defined(PGPU_PART) && (PGPU_PART == 36 || PGPU_PART == 37)
 #include "hensel_wave_n2.hpp"   // ... for the n^2 domain: DJN encrypt and CT x PT of small batches on pair rows
 #endif
+#if defined(PGPU_PART) && PGPU_PART >= 38 && PGPU_PART <= 40
+#include "hensel_matvec.hpp"    // the encrypted matrix-vector product: shared window tables + multi-exponentiation
+#endif
 
 #ifndef PGPU_PART
-#error "compile with -DPGPU_PART=0..37 (15 and 30 are retired)"
+#error "compile with -DPGPU_PART=0..40 (15 and 30 are retired)"
 #endif
 
 namespace pgpu {
@@ -426,6 +429,27 @@ bool launch_hensel_modexp_part6(int H, int K, const HenselModexpArgs& a, unsigne
     return true;
   }
   return false;
+}
+#elif PGPU_PART >= 38 && PGPU_PART <= 40
+// the encrypted matrix-vector product (hensel_matvec.hpp): table build and multi-exponentiation of one geometry per part
+#if PGPU_PART == 38
+#define PGPU_MV_G 4
+#define PGPU_MV_K 18
+#define PGPU_MV_NAME launch_matvec_part38
+#elif PGPU_PART == 39
+#define PGPU_MV_G 8
+#define PGPU_MV_K 14
+#define PGPU_MV_NAME launch_matvec_part39
+#else
+#define PGPU_MV_G 2
+#define PGPU_MV_K 19
+#define PGPU_MV_NAME launch_matvec_part40
+#endif
+bool PGPU_MV_NAME(int G, int K, bool table, const MatvecArgs& a, unsigned blocks, hipStream_t s) {
+  if (G != PGPU_MV_G || K != PGPU_MV_K) return false;
+  if (table) hipLaunchKernelGGL((matvec_table_kernel<PGPU_MV_G, PGPU_MV_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
+  else hipLaunchKernelGGL((matvec_kernel<PGPU_MV_G, PGPU_MV_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
+  return true;
 }
 #else
 bool launch_hensel_part2(int H, int K, const HenselArgs& a, unsigned blocks, hipStream_t s) {

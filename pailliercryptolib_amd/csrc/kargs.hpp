@@ -282,6 +282,22 @@ struct PairOpsArgs {
   size_t count;
 };
 
+// Encrypted matrix-vector product on pair rows (hensel_matvec.hpp): out[i] = prod_j x[j]^w[i][j] as a simultaneous
+// fixed-window multi-exponentiation.  Both kernels of a call take the same arguments.
+struct MatvecArgs {
+  HenselPubDev ctx;
+  const uint32_t* x;         // [cols][2*L2] the encrypted vector as pair rows (matvec_table_kernel)
+  uint32_t* table;           // [cols][2^window][2*L2] T[j][d] = x[j]^d, shared by all rows of the call
+  const uint64_t* w;         // [rows*cols][w_stride] the plaintext matrix, row-major, each value < 2^e_bits
+  size_t w_stride;
+  int w_words;               // valid words per value
+  int e_bits;                // >= 1
+  int window;                // 1..6
+  int slices;                // 1..cols: column ranges with a partial product each
+  size_t rows, cols;
+  uint32_t* out;             // [slices][rows][2*L2] partial products as pair rows (matvec_kernel)
+};
+
 struct FixedBaseArgs {
   ModCtxDev ctx;         // modulus n^2 (nr set)
   const uint32_t* table; // [nwin][2^w][L]

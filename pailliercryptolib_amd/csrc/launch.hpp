@@ -283,6 +283,21 @@ inline bool launch_pair_mul_seq(int G, int K, const PairOpsArgs& a, unsigned blo
   return launch_pair_mul_seq_part19(G, K, a, blocks, s) || launch_pair_mul_seq_part27(G, K, a, blocks, s);
 }
 
+// The encrypted matrix-vector product (hensel_matvec.hpp; k_hensel.hip parts 38-40): the window tables of the columns and
+// the multi-exponentiation, in the sequential-halves geometries of the three key classes that have pair rows
+inline bool matvec_has(int G, int K) { return (G == 4 && K == 18) || (G == 8 && K == 14) || (G == 2 && K == 19); }
+bool launch_matvec_part38(int G, int K, bool table, const MatvecArgs& a, unsigned blocks, hipStream_t s);
+bool launch_matvec_part39(int G, int K, bool table, const MatvecArgs& a, unsigned blocks, hipStream_t s);
+bool launch_matvec_part40(int G, int K, bool table, const MatvecArgs& a, unsigned blocks, hipStream_t s);
+inline bool launch_matvec_table(int G, int K, const MatvecArgs& a, unsigned blocks, hipStream_t s) {
+  return launch_matvec_part38(G, K, true, a, blocks, s) || launch_matvec_part39(G, K, true, a, blocks, s) ||
+         launch_matvec_part40(G, K, true, a, blocks, s);
+}
+inline bool launch_matvec(int G, int K, const MatvecArgs& a, unsigned blocks, hipStream_t s) {
+  return launch_matvec_part38(G, K, false, a, blocks, s) || launch_matvec_part39(G, K, false, a, blocks, s) ||
+         launch_matvec_part40(G, K, false, a, blocks, s);
+}
+
 // DJN encrypt to pair rows in the same form (k_hensel.hip parts 20, 21, 28): (4,18) 2048-bit keys, (8,14) 3072, (2,19) 1024
 inline bool hensel_fb_encrypt_seq_has(int G, int K) { return (G == 4 && K == 18) || (G == 8 && K == 14) || (G == 2 && K == 19); }
 bool launch_hensel_fb_encrypt_seq_part28(int G, int K, const HenselFbArgs& a, unsigned blocks, hipStream_t s);

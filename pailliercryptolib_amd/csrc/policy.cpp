@@ -179,5 +179,52 @@ int pick_decrypt_window(int exp_bits, size_t entry_bytes) {
 // 11 % more products: 26 ms (lone paired launch: 6.6 -> 6.0 ms against 4.6 indexed).
 int masked_decrypt_window() { return 3; }
 
+// ---- encrypted matrix-vector product ----
+// (the knobs are read at every call, not once: a test process walks through several forced shapes)
+static long env_now(const char* name) {
+  const char* e = std::getenv(name);
+  return e && *e ? std::atol(e) : 0;
+}
+bool matvec_geometry(int key_bits, int* G, int* K) {
+  // the rule of build_hensel_pub (capi_keys.inc) for the form of fewest lanes: 29 * G * K >= bits of n + 29 + 8
+  static const int forms[3][2] = {{2, 19}, {4, 18}, {8, 14}};
+  if (key_bits < 1) return false;
+  for (const auto& f : forms) {
+    if (pgpu::kLimbBits * f[0] * f[1] >= key_bits + pgpu::kLimbBits + 8 && pgpu::matvec_has(f[0], f[1])) {
+      if (G) *G = f[0];
+      if (K) *K = f[1];
+      return true;
+    }
+  }
+  return false;
+}
+size_t matvec_slices(int G, size_t rows, size_t cols) {
+  if (rows == 0 || cols == 0) return 1;
+  const long forced = env_now("PGPU_MATVEC_SLICES");
+  if (forced > 0) return std::min((size_t)forced, cols);
+  const size_t ipw = 64 / (size_t)G;
+  const size_t row_waves = (rows + ipw - 1) / ipw;               // wavefronts of one slice
+  const size_t fill = (kSimds + row_waves - 1) / row_waves;      // slices that put a wavefront on every SIMD
+  const size_t cap = std::max<size_t>(1, cols / kMatvecMinSliceCols);
+  return std::max<size_t>(1, std::min(std::min(fill, cap), cols));
+}
+double matvec_products(size_t rows, size_t cols, int e_bits, int w, size_t slices) {
+  const double nwin = (double)((e_bits + w - 1) / w);
+  return (double)cols * (double)(((size_t)1 << w) - 2) + (double)rows * (double)slices * (double)e_bits +
+         (double)rows * (double)cols * nwin + (double)rows * (double)(slices - 1);
+}
+int matvec_window(size_t rows, size_t cols, int e_bits, size_t slices, size_t row_bytes) {
+  const long forced = env_now("PGPU_MATVEC_WINDOW");
+  if (forced > 0) return (int)std::min(forced, 6L);
+  int best = 1;
+  double best_cost = matvec_products(rows, cols, e_bits, 1, slices);
+  for (int w = 2; w <= 6; ++w) {
+    if ((double)cols * (double)((size_t)1 << w) * (double)row_bytes > (double)kMatvecTableCap) break;
+    const double cost = matvec_products(rows, cols, e_bits, w, slices);
+    if (cost < best_cost) { best_cost = cost; best = w; }
+  }
+  return best;
+}
+
 }  // namespace policy
 }  // namespace pgpu

@@ -74,6 +74,30 @@ int pick_decrypt_window(int exp_bits, size_t entry_bytes = 0);
 // ... under the masked table gather (every entry of the table read at every window product: small on purpose)
 int masked_decrypt_window();
 
+
+// ---- the encrypted matrix-vector product (hensel_matvec.hpp; pgpu_batch_ct_matvec, pgpu_ct_matvec_plan) ----
+// Y[i] = prod_j X[j]^W[i][j] as an interleaved fixed-window multi-exponentiation: window tables of the cols ciphertexts
+// shared by all rows, one group of G lanes per (row, column slice).  Counted in pair products a call costs
+//     cols * (2^w - 2)                table build
+//   + rows * S * e_bits               squarings (every slice runs its own chain)
+//   + rows * cols * ceil(e_bits / w)  multiplications by table entries
+//   + rows * (S - 1)                  fold of the partial products.
+// Geometry of the key class (the sequential-halves forms of hensel_modexp_seq_kernel): (2,19) up to 1065-bit n, (4,18) up
+// to 2051, (8,14) up to 3211; false: the class has no pair rows (4096-bit keys).
+bool matvec_geometry(int key_bits, int* G, int* K);
+// S: the smallest slice count that puts a wavefront on every SIMD -- a wavefront holds 64/G rows of one slice -- but a
+// slice keeps at least kMatvecMinSliceCols columns, so that the e_bits squarings every slice repeats stay at most
+// w / (w + kMatvecMinSliceCols) of its products; where the rows alone fill the chip S = 1.  1 <= S <= cols.
+// PGPU_MATVEC_SLICES=S forces it (clamped to 1..cols; read at every call: the tests reach every path with it).
+constexpr size_t kMatvecMinSliceCols = 4;
+size_t matvec_slices(int G, size_t rows, size_t cols);
+// w in 1..6 with the fewest products above, among those whose table (cols * 2^w rows of row_bytes) stays under
+// kMatvecTableCap -- the Infinity Cache, which the multiply path reads its entries from.  PGPU_MATVEC_WINDOW=w forces it.
+constexpr size_t kMatvecTableCap = (size_t)256 << 20;
+int matvec_window(size_t rows, size_t cols, int e_bits, size_t slices, size_t row_bytes);
+// products of the schedule above (w, S as given)
+double matvec_products(size_t rows, size_t cols, int e_bits, int w, size_t slices);
+
 }  // namespace policy
 }  // namespace pgpu
 

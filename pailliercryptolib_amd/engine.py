@@ -148,6 +148,37 @@ class PublicKey:
             raise RuntimeError("encrypt: Cannot encrypt empty PlainText")
         return limbs_to_ints(self.encrypt_limbs(ints_to_limbs(m, mw), ints_to_limbs(r, rw)))
 
+    def matvec(self, x, w, e_bits=None):
+        """Encrypted matrix-vector product: x a list of ciphertexts (ints modulo n^2), w a plaintext matrix (a list of
+        rows, or one flat row for a dot product) of non-negative ints -> the list of ciphertexts
+        prod_j x[j]^w[i][j] mod n^2, i.e. encryptions of (w @ m) mod n.  One pgpu_batch_ct_matvec call on resident batches
+        (a shared-table multi-exponentiation); there is no element-wise fall-back."""
+        rows = [list(r) for r in w] if len(w) and isinstance(w[0], (list, tuple)) else [list(w)]
+        cols = len(x)
+        if cols == 0 or not rows or any(len(r) != cols for r in rows):
+            raise RuntimeError("matvec error: Size mismatch!")
+        flat = [int(v) for r in rows for v in r]
+        if min(flat) < 0:
+            raise RuntimeError("matvec error: negative weights have no encoding (pass w mod n)")
+        if e_bits is None:
+            e_bits = max(1, max(v.bit_length() for v in flat))
+        ew = (int(e_bits) + 63) // 64
+        L = _capi.lib()
+        W = 2 * self.n_words
+        hx, hw, ho = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        try:
+            xa, wa = ints_to_limbs([int(v) for v in x], W), ints_to_limbs(flat, ew)
+            _capi.check(L.pgpu_batch_upload(_ptr(xa), cols, W, W, ctypes.byref(hx)))
+            _capi.check(L.pgpu_batch_upload(_ptr(wa), len(flat), ew, ew, ctypes.byref(hw)))
+            _capi.check(L.pgpu_batch_ct_matvec(self._h, hx, hw, len(rows), int(e_bits), ctypes.byref(ho)))
+            out = np.empty((len(rows), W), dtype=np.uint64)
+            _capi.check(L.pgpu_batch_download(ho, _ptr(out)))
+        finally:
+            for h in (hx, hw, ho):
+                if h:
+                    L.pgpu_batch_destroy(h)
+        return limbs_to_ints(out)
+
 
 class PrivateKey:
     """Host-side mirror of ipcl::PrivateKey::decrypt (CRT path, pri_key.cpp:65-90,114-157)."""
