@@ -389,6 +389,7 @@ int make_schedule(const BigNumber& e, int w, ExpSchedule* out, bool secret) {
 constexpr int kFbMaxW = 14;        // (the kernels take any width; the table budgets narrow it -- fb_fit_window)
 // 13 since round 4: 79 products for a 1024-bit r instead of 86 (encrypt launch of the bench 0.835 -> 0.775 ms, step +1 %),
 // 373 MB of table per 2048-bit key and GPU instead of 203 MB, built in 73 ms instead of 40
+// (unit-factor form, fb_table_for_split: the same bytes, about 145 ms with the second pass and the host's inversion)
 constexpr int kFbDefaultW = 13;
 constexpr int kFbMaskedMaxW = 5;   // tables of windows up to this width belong to the masked product (kept beside the indexed table)
 std::atomic<int> g_fb_window{-1};
@@ -581,9 +582,18 @@ int run_modexp(rt::Device& d, pgpu::ModexpArgs& a, const GeoInfo& ctx_geo, hipSt
 }  // namespace
 
 // ---------- Paillier key objects ----------
+// Two forms, never mixed: the full-width tables (key->fb) hold the residues themselves; the split-form tables (key->fbh) hold
+// UNIT-FACTOR entries (alpha, beta), g*R == alpha * (1 + n*beta) mod n^2 (hensel.hpp: hensel_fb_build_kernel) -- same entry size
+// as the pair (a, b) they replace.  The encrypt kernels of hensel*.hpp multiply by (alpha, 0) and add the betas: a table of
+// plain pairs would give wrong ciphertexts under them, hence the tag, set by the builder and checked before every launch.
+// As the code stands the check cannot fail -- key->fbh is filled by fb_table_for_split alone, key->fb by fb_table_for alone,
+// and a table never outlives the process that built it: it is a tripwire for whoever adds a third builder or shares a list,
+// not a guard against stale tables.
+enum FbForm : int { FB_FORM_FULL = 0, FB_FORM_UNIT_FACTOR = 1 };
 struct FbTable {   // immutable once built: hs^(d * 2^(w*i)) * R, [nwin][2^w][L]
   void* p = nullptr;
   int w = 0, nwin = 0;
+  int form = FB_FORM_FULL;
   hipEvent_t ready = nullptr;   // recorded behind the build; launches on other streams wait for it
   size_t bytes = 0;
   uint64_t tick = 0;            // last use (LRU over all keys of a device)
@@ -1138,10 +1148,14 @@ struct FbPin {
 };
 
 // Looks up / builds the table of (key, device) for window w covering nwin windows.  `build` queues the build kernel
-// on s for a freshly allocated table; entry_bytes: bytes per table entry.
+// on s for a freshly allocated table; entry_bytes: bytes per table entry; scratch_bytes: what `build` allocates on top of the
+// table while it runs (room is made for both, only the table is counted afterwards).
+// g_fb_mu is held across `build`.  The full-width build is one asynchronous launch; the split-form build
+// (fb_table_for_split) synchronises the stream twice and works on the host in between, about 0.15 s for a 2048-bit key at
+// w = 13: every thread that needs ANY fixed-base table waits that long, once per key and GPU.
 template <class Build>
 int fb_table_get(const pgpu_pubkey* key, std::vector<std::list<FbTable>>& lists, rt::Device& d, int w, int nwin,
-                 size_t entry_bytes, hipStream_t s, FbPin* out, Build build) {
+                 size_t entry_bytes, size_t scratch_bytes, hipStream_t s, FbPin* out, Build build) {
   std::lock_guard<std::mutex> lk(g_fb_mu);
   if (lists.size() < (size_t)rt::pool_size()) lists.resize((size_t)rt::pool_size());
   auto& list = lists[(size_t)d.index];
@@ -1169,7 +1183,7 @@ int fb_table_get(const pgpu_pubkey* key, std::vector<std::list<FbTable>>& lists,
   t.w = w;
   t.nwin = nwin;
   t.bytes = (size_t)nwin * ((size_t)1 << w) * entry_bytes;
-  fb_make_room(d.index, t.bytes);
+  fb_make_room(d.index, t.bytes + scratch_bytes);
   hipError_t e = hipMalloc(&t.p, t.bytes);
   if (e != hipSuccess) return fail(PGPU_ERR_HIP, std::string("fixed-base table: ") + hipGetErrorString(e));
   if (hipEventCreateWithFlags(&t.ready, hipEventDefault) != hipSuccess || hipEventCreateWithFlags(&t.t0, hipEventDefault) != hipSuccess) {
@@ -1197,7 +1211,7 @@ int fb_table_get(const pgpu_pubkey* key, std::vector<std::list<FbTable>>& lists,
 // fixed-base table of (key, device) for window w covering nwin windows: built on first use
 int fb_table_for(const pgpu_pubkey* key, rt::Device& d, int w, int nwin, hipStream_t s, FbPin* out) {
   const GeoInfo& geo = key->nsq->geo;
-  return fb_table_get(key, key->fb, d, w, nwin, (size_t)geo.L() * sizeof(uint32_t), s, out, [&](FbTable& t) -> int {
+  return fb_table_get(key, key->fb, d, w, nwin, (size_t)geo.L() * sizeof(uint32_t), 0, s, out, [&](FbTable& t) -> int {
     pgpu::FixedBaseBuildArgs b{};
     b.ctx = key->nsq->view(d.index);
     b.base = (const uint64_t*)key->d_hs.d[(size_t)d.index];
@@ -1385,11 +1399,26 @@ int modexp_split_on(rt::Device& d, const pgpu_pubkey* key, const pgpu_pubkey::Pu
   t.stop();
   return PGPU_OK;
 }
-// the fixed-base table of pairs (hensel.hpp: hensel_fb_build_kernel); same size as the full-width one
+// the fixed-base table of the split form in unit-factor form (hensel.hpp: hensel_fb_build_kernel); same size as the full-width
+// one.  Two launches with the host in between: hensel_fb_build_kernel leaves the pairs, the running products of their a parts
+// modulo n (scratch, half a table, freed here; fb_table_get makes room for it beside the table) and one total per row -- per
+// segment of 1024 entries for longer rows, so that the walks back run side by side --; the host inverts the totals (ONE modular
+// inversion: simultaneous inversion once more); hensel_fb_unit_factor_kernel walks back and stores beta over every b part.
+// Once per key and device, outside any timed region; synchronous, and under g_fb_mu (see fb_table_get).
 int fb_table_for_split(const pgpu_pubkey* key, const pgpu_pubkey::PubForm* form, rt::Device& d, int w, int nwin,
                        hipStream_t s, FbPin* out) {
   const int H = form->H, K = form->K;
-  return fb_table_get(key, key->fbh, d, w, nwin, (size_t)2 * H * K * sizeof(uint32_t), s, out, [&](FbTable& t) -> int {
+  const int L2 = H * K;
+  const int seg_len = std::max(2, std::min(1 << w, 1024)), nseg = (1 << w) / seg_len;
+  const size_t ntot = (size_t)nwin * nseg, rowl = ntot * L2;
+  const size_t pre_bytes = ((size_t)nwin << w) * L2 * sizeof(uint32_t), io_bytes = 2 * rowl * sizeof(uint32_t);
+  return fb_table_get(key, key->fbh, d, w, nwin, (size_t)2 * H * K * sizeof(uint32_t), pre_bytes + io_bytes, s, out, [&](FbTable& t) -> int {
+    struct Scratch {
+      void* p = nullptr;
+      ~Scratch() { if (p) (void)hipFree(p); }
+    } pre, io;
+    HIP_TRY(hipMalloc(&pre.p, pre_bytes));
+    HIP_TRY(hipMalloc(&io.p, io_bytes));
     pgpu::HenselFbBuildArgs b{};
     b.ctx = hensel_pub_view(form, d.index);
     b.base = (const uint64_t*)key->d_hs.d[(size_t)d.index];
@@ -1399,10 +1428,55 @@ int fb_table_for_split(const pgpu_pubkey* key, const pgpu_pubkey::PubForm* form,
     b.table = (uint32_t*)t.p;
     b.nwin = nwin;
     b.w = w;
+    b.seg_len = seg_len;
+    b.prefix = (uint32_t*)pre.p;
+    b.total = (uint32_t*)io.p;
     const int ipw = 64 / (2 * H);
     const unsigned blocks = (unsigned)((((size_t)nwin + ipw - 1) / ipw + pgpu::kWavesPerWG - 1) / pgpu::kWavesPerWG);
     if (!pgpu::launch_hensel_fb_build(H, K, b, blocks, s))
       return fail(PGPU_ERR_UNSUPPORTED, "split-form fixed-base build kernel not compiled");
+    std::vector<uint32_t> h(rowl);
+    HIP_TRY(hipMemcpyAsync(h.data(), b.total, rowl * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    // u = total^-1 * R * (-k) mod n per segment; the inverses from ONE inversion of the product of all totals
+    const BigNumber& n = form->n;
+    const BigNumber scale = ((pow2(L2 * pgpu::kLimbBits) % n) * (n - BigNumber((Ipp32u)form->n0inv) % n)) % n;
+    std::vector<uint64_t> words(((size_t)L2 * pgpu::kLimbBits + 63) / 64 + 1);
+    std::vector<BigNumber> tot(ntot), before(ntot);
+    BigNumber acc((Ipp32u)1);
+    for (size_t i = 0; i < ntot; ++i) {
+      std::fill(words.begin(), words.end(), 0);
+      for (int j = 0; j < L2; ++j) {      // canonical 29-bit limbs -> 64-bit words
+        const size_t bit = (size_t)j * pgpu::kLimbBits;
+        const uint64_t v = h[i * L2 + j];
+        words[bit >> 6] |= v << (bit & 63);
+        if ((bit & 63) + pgpu::kLimbBits > 64) words[(bit >> 6) + 1] |= v >> (64 - (bit & 63));
+      }
+      tot[i] = BigNumber::fromLimbs64(words.data(), words.size()) % n;
+      if (tot[i].isZero()) return fail(PGPU_ERR_INVALID_PARAM, "fixed-base table: hs is not a unit modulo n");
+      before[i] = acc;
+      acc = (acc * tot[i]) % n;
+    }
+    BigNumber inv = n.InverseMul(acc);
+    for (size_t i = ntot; i-- > 0;) {
+      to_limbs29((((inv * before[i]) % n) * scale) % n, L2, h.data() + i * L2);
+      inv = (inv * tot[i]) % n;
+    }
+    pgpu::HenselFbUnitArgs u{};
+    u.n = b.ctx.n;
+    u.n0inv = b.ctx.n0inv;
+    u.table = b.table;
+    u.nwin = nwin;
+    u.w = w;
+    u.seg_len = seg_len;
+    u.prefix = b.prefix;
+    u.uinit = (uint32_t*)io.p + rowl;
+    HIP_TRY(hipMemcpyAsync((void*)u.uinit, h.data(), rowl * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    const unsigned blocks1 = (unsigned)(((ntot + ipw - 1) / ipw + pgpu::kWavesPerWG - 1) / pgpu::kWavesPerWG);
+    if (!pgpu::launch_hensel_fb_unit_factor(H, K, u, blocks1, s))
+      return fail(PGPU_ERR_UNSUPPORTED, "split-form fixed-base build kernel not compiled");
+    HIP_TRY(hipStreamSynchronize(s));   // (h and the scratch go out of scope)
+    t.form = FB_FORM_UNIT_FACTOR;
     return PGPU_OK;
   });
 }
@@ -1443,6 +1517,7 @@ int encrypt_on(rt::Device& d, const pgpu_pubkey* key, const uint64_t* d_m, size_
     // no wider than n, and a batch that fills the chip in 8-lane groups no worse than the full-width kernel does
     if (const pgpu_pubkey::PubForm* form = sform) {
       RC_TRY(fb_table_for_split(key, form, d, fbw, nwin, s, &tab));
+      if (tab->form != FB_FORM_UNIT_FACTOR) return fail(PGPU_ERR_UNSUPPORTED, "split-form encrypt needs a unit-factor table");
       // pair-row output of a batch that leaves SIMDs idle: the encrypt kernel of a form with more lanes per element and
       // the SAME limbs per half (2048-bit keys: (8,9) beside (4,18)) -- same table, same rows, shorter serial chain
       if (d_pair) {
@@ -1508,6 +1583,7 @@ int encrypt_on(rt::Device& d, const pgpu_pubkey* key, const uint64_t* d_m, size_
       return PGPU_OK;
     }
     RC_TRY(fb_table_for(key, d, fbw, nwin, s, &tab));
+    if (tab->form != FB_FORM_FULL) return fail(PGPU_ERR_UNSUPPORTED, "full-width encrypt needs a table of residues");
     pgpu::FixedBaseArgs f{};
     f.ctx = key->nsq->view(d.index, vflags);
     f.table = (const uint32_t*)tab->p;

@@ -58,8 +58,8 @@ __device__ __forceinline__ uint32_t pair_row(uint32_t src) {
 
 // One K-row block of a pair product.  mc: this lane's multiplicand limbs for the rows of csrc (half A: a,
 // half B: b; a squaring doubles half B's); md / asrc: the second product of half B (d times the rows of a; md is
-// zero in half A, unused in a squaring).
-template <int H, int K, bool SQR, bool UNITQ, int S>
+// zero in half A, unused in a squaring).  DZ: d is zero (a fixed-base table entry in unit-factor form): no second product.
+template <int H, int K, bool SQR, bool UNITQ, int S, bool DZ = false>
 __device__ __forceinline__ void pair_block(uint64_t (&LOWC)[K], uint64_t (&UPC)[K], const uint32_t (&mc)[K],
                                            const uint32_t (&md)[K], const uint32_t (&csrc)[K],
                                            const uint32_t (&asrc)[K], const uint32_t (&n)[K], uint32_t n0inv,
@@ -77,7 +77,7 @@ __device__ __forceinline__ void pair_block(uint64_t (&LOWC)[K], uint64_t (&UPC)[
       else UPC[r + j - K] += p;
     }
   }
-  if constexpr (!SQR) {
+  if constexpr (!SQR && !DZ) {
     uint32_t arow[K];
 #pragma unroll
     for (int r = 0; r < K; ++r) arow[r] = pair_row<H, S>(asrc[r]);
@@ -96,37 +96,44 @@ __device__ __forceinline__ void pair_block(uint64_t (&LOWC)[K], uint64_t (&UPC)[
 
 // r = own (x) m: the Montgomery product of two pairs (lazy: inputs < 8P -> outputs < 2P).  own, m, r: this lane's
 // K limbs (half A: the a part, half B: the b part).  halfB: 1 in the upper H lanes; selB: 1 in lane H of the group.
-template <int H, int K, bool SQR, bool UNITQ, int S>
+template <int H, int K, bool SQR, bool UNITQ, int S, bool DZ = false>
 __device__ __forceinline__ void pair_blocks(uint64_t (&c0)[K], uint64_t (&c1)[K], const uint32_t (&mc)[K],
                                             const uint32_t (&md)[K], const uint32_t (&csrc)[K],
                                             const uint32_t (&asrc)[K], const uint32_t (&n)[K], uint32_t n0inv,
                                             uint32_t selB) {
   if constexpr (S < H) {
-    pair_block<H, K, SQR, UNITQ, S>(c0, c1, mc, md, csrc, asrc, n, n0inv, selB);
-    pair_block<H, K, SQR, UNITQ, S + 1>(c1, c0, mc, md, csrc, asrc, n, n0inv, selB);
-    pair_blocks<H, K, SQR, UNITQ, S + 2>(c0, c1, mc, md, csrc, asrc, n, n0inv, selB);
+    pair_block<H, K, SQR, UNITQ, S, DZ>(c0, c1, mc, md, csrc, asrc, n, n0inv, selB);
+    pair_block<H, K, SQR, UNITQ, S + 1, DZ>(c1, c0, mc, md, csrc, asrc, n, n0inv, selB);
+    pair_blocks<H, K, SQR, UNITQ, S + 2, DZ>(c0, c1, mc, md, csrc, asrc, n, n0inv, selB);
   }
 }
-template <int H, int K, bool SQR, bool UNITQ>
+// (DZ: the operand m is (c, 0) whatever half B's limbs of m hold -- they are not read)
+template <int H, int K, bool SQR, bool UNITQ, bool DZ = false>
 __device__ __forceinline__ void pairmul(uint32_t (&r)[K], const uint32_t (&own)[K], const uint32_t (&m)[K],
                                         const uint32_t (&n)[K], uint32_t n0inv, uint32_t halfB, uint32_t selB) {
+  static_assert(!(SQR && DZ), "a squaring has no zero operand");
   static_assert(3 * K + 6 < 64, "a column of half B receives 3K products (+ relaxed limbs): must stay below 2^64");
   static_assert(H == 2 || H == 4 || H == 8, "two halves inside one 16-lane DPP row");
   using GEO = Geo<H, K>;
   uint64_t c0[K], c1[K];
   uint32_t mc[K], md[K], csrc[K], asrc[K];
   const uint32_t maskB = 0u - halfB;
-  pair_row_source<H, K>(asrc, own);                     // rows of a (a squaring: the only rows)
+  if constexpr (!DZ) {
+    pair_row_source<H, K>(asrc, own);                   // rows of a (a squaring: the only rows)
+  } else {
+#pragma unroll
+    for (int j = 0; j < K; ++j) asrc[j] = 0;            // (not read)
+  }
   if constexpr (!SQR) pair_row_source<H, K>(csrc, m);   // rows of c
 #pragma unroll
   for (int j = 0; j < K; ++j) {
     c0[j] = 0;
     c1[j] = 0;
     mc[j] = SQR ? own[j] << halfB : own[j];   // squaring: half B accumulates 2*a*b
-    md[j] = SQR ? 0 : m[j] & maskB;
+    md[j] = (SQR || DZ) ? 0 : m[j] & maskB;
   }
   if constexpr (SQR) pair_blocks<H, K, SQR, UNITQ, 0>(c0, c1, mc, md, asrc, asrc, n, n0inv, selB);
-  else pair_blocks<H, K, SQR, UNITQ, 0>(c0, c1, mc, md, csrc, asrc, n, n0inv, selB);
+  else pair_blocks<H, K, SQR, UNITQ, 0, DZ>(c0, c1, mc, md, csrc, asrc, n, n0inv, selB);
   montmul_finish<GEO>(r, c0);
 }
 
@@ -445,16 +452,16 @@ __device__ __forceinline__ void store_pair_row(uint32_t* __restrict__ row, const
 // (montmul(m, gm) = -k^-1*m*R, then times a), instead of the pair product by the pair of g^m (CT + PT:
 // ciphertext.cpp:75-80; the g^m factor of encrypt: pub_key.cpp:88-105).  mwords: the group's plaintext words in LDS
 // (zero padded to W64+1 of the half width); both halves run the same instruction stream.
+// (mv: the limbs of m, lane-distributed in each half; relaxed, any value below R / 4)
 template <int H, int K>
-__device__ __forceinline__ void pair_times_gm(uint32_t (&own)[K], const HenselPubDev& C, const uint64_t* mwords, int x,
-                                              uint32_t halfB) {
+__device__ __forceinline__ void pair_times_gm_limbs(uint32_t (&own)[K], const HenselPubDev& C, const uint32_t (&mv)[K], int x,
+                                                    uint32_t halfB) {
   using HG = Geo<H, K>;
-  uint32_t n[K], mv[K], cg[K], u[K], av[K], v[K];
+  uint32_t n[K], cg[K], u[K], av[K], v[K];
 #pragma unroll
   for (int j = 0; j < K; ++j) {
     n[j] = C.n[x * K + j];
     cg[j] = C.gm[x * K + j];
-    mv[j] = limb_from_words(mwords, x * K + j);
   }
   montmul_reg<HG, false, false>(u, mv, cg, n, C.n0inv);
 #pragma unroll
@@ -466,6 +473,14 @@ __device__ __forceinline__ void pair_times_gm(uint32_t (&own)[K], const HenselPu
 #pragma unroll
   for (int j = 0; j < K; ++j) v[j] = halfB ? v[j] : 0u;
   add_normalise<HG>(own, v);
+}
+template <int H, int K>
+__device__ __forceinline__ void pair_times_gm(uint32_t (&own)[K], const HenselPubDev& C, const uint64_t* mwords, int x,
+                                              uint32_t halfB) {
+  uint32_t mv[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) mv[j] = limb_from_words(mwords, x * K + j);
+  pair_times_gm_limbs<H, K>(own, C, mv, x, halfB);
 }
 
 // own = words * R as a pair: sum over the chunks z_i of (z_i, 0) (x) pair(2^(64*cw*i) * R^2).  iorow: the group's
@@ -588,12 +603,25 @@ __device__ __forceinline__ void pair_exit_store(uint32_t (&own)[K], const Hensel
   store_canonical<FG>(t, nf, F.mod_words, bl, io, out, out_stride, first_inst, count, lane, grp, xg);
 }
 
-// Fixed-base table of pairs for the DJN obfuscator hs^r (kernels.hpp: fb_build_kernel is the full-width twin):
-// group i builds row i, T[i][d] = hs^(d * 2^(w*i)) * R as a pair.
+// Fixed-base table for the DJN obfuscator hs^r (kernels.hpp: fb_build_kernel is the full-width twin), in UNIT-FACTOR form.
+// Group i builds row i.  This kernel computes T[i][d] = hs^(d * 2^(w*i)) * R as a pair (a_d, b_d) == a_d - P*b_d, as ever.  Modulo
+// n^2 (P = n*k, a_d a unit modulo n since the entry is one modulo n^2):
+//        a_d - P*b_d  ==  a_d * (1 + n*beta_d),      beta_d = (-k * b_d * a_d^-1) mod n          (a_d^-1 modulo the TRUE modulus n)
+// and a second kernel, hensel_fb_unit_factor_kernel, stores beta_d (canonical limbs) in place of b_d: same entry size, same addressing.  A product of entries is then
+//        prod (a_i, 0)  times  (1 + n * sum beta_i)        (mod n^2)
+// -- pair products by (a_i, 0) cost two half-width products instead of three, the beta_i are ADDED, and the sum joins the
+// plaintext in the 1 + n*m product the encrypt kernels end with anyway (hensel_fb_encrypt_kernel).
+// The inverses come by simultaneous inversion along the walk a group makes over its row anyway, all under the true modulus n
+// (M(x, y) = x*y*R^-1 mod n):  this kernel leaves the running products p_d = M(p_(d-1), a_d), p_0 = a_0, in A.prefix and p_(T-1) in
+// A.total; the host inverts that ONE value per row and hands back u_(T-1) = p_(T-1)^-1 * R * (-k) mod n; hensel_fb_unit_factor_kernel walks
+// down with the invariant u_d = p_d^-1 * R * (-k)  (long rows: per segment of A.seg_len entries, so that the walks run side by side):
+//        ia = M(u_d, p_(d-1)) = a_d^-1 * R * (-k)   (d = 0: ia = u_0)       beta_d = M(b_d, ia)       u_(d-1) = M(u_d, a_d)
+// -- half A's lanes run M(u_d, a_d) while half B's run M(u_d, p_(d-1)): two half-width products per entry.
+// The table is a function of the public key alone.
 template <int H, int K>
 __global__ __launch_bounds__(kWGThreads, K <= 14 ? 2 : 1) void hensel_fb_build_kernel(HenselFbBuildArgs A) {
   using HG = Geo<H, K>;
-  constexpr int GS = 2 * H, IPW = kWave / GS, LQ = 2 * H * K, W64 = HG::W64;
+  constexpr int GS = 2 * H, IPW = kWave / GS, L2 = H * K, LQ = 2 * H * K, W64 = HG::W64;
   __shared__ uint64_t io_[kWavesPerWG][IPW][W64 + 1];
   const int lane = threadIdx.x % kWave, wv = threadIdx.x / kWave;
   auto& io = io_[wv];
@@ -605,11 +633,20 @@ __global__ __launch_bounds__(kWGThreads, K <= 14 ? 2 : 1) void hensel_fb_build_k
   size_t inst = first_inst + grp;
   const bool live = inst < (size_t)A.nwin;
   if (!live) inst = (size_t)A.nwin - 1;
-  uint32_t n[K], own[K], mreg[K];
+  const int tsize = 1 << A.w;
+  // rows of more than A.seg_len entries are inverted in SEGMENTS of that many (a power of two >= 2), each with its own running
+  // products and total: the second pass then has nwin * nseg walks of seg_len entries instead of nwin walks of 2^w
+  const int seg_len = A.seg_len, nseg = tsize / seg_len;
+  uint32_t* row = A.table + inst * (size_t)tsize * LQ + xg * K;
+  uint32_t* pre = A.prefix + inst * (size_t)tsize * L2 + x * K;   // (written by half A's lanes)
+  uint32_t nt[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) nt[j] = A.ctx.n[x * K + j];
+  const uint32_t n0t = A.ctx.n0inv;
+  uint32_t n[K], own[K], mreg[K], pr[K];
 #pragma unroll
   for (int j = 0; j < K; ++j) n[j] = A.ctx.nhat[x * K + j];
   pair_from_words<H, K>(own, A.base, A.base_words, A.chunk_words, A.nchunks, A.ctx.conv, io[grp], n, halfB, selB, xg);
-  const int tsize = 1 << A.w;
   // every group runs the squaring count of the LAST live row of its wavefront (uniform control flow); a group stops
   // updating once its own count is reached
   const int my_sq = A.w * (int)inst;
@@ -625,30 +662,127 @@ __global__ __launch_bounds__(kWGThreads, K <= 14 ? 2 : 1) void hensel_fb_build_k
       for (int j = 0; j < K; ++j) own[j] = r[j];
     }
   }
-  uint32_t* row = A.table + inst * (size_t)tsize * LQ + xg * K;
+  const bool keepA = live && !halfB;
+  // the running products of the a parts under the true modulus (half A's lanes; half B's run along on its b parts, unused)
+#pragma unroll
+  for (int j = 0; j < K; ++j) mreg[j] = A.ctx.one[xg * K + j];
+  montmul_reg<HG, false, false>(pr, mreg, own, nt, n0t);
   if (live) {
 #pragma unroll
     for (int j = 0; j < K; ++j) {
-      row[j] = A.ctx.one[xg * K + j];
+      row[j] = mreg[j];
       row[LQ + j] = own[j];
+    }
+  }
+  if (keepA) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      pre[j] = mreg[j];
+      pre[L2 + j] = pr[j];
     }
   }
 #pragma unroll
   for (int j = 0; j < K; ++j) mreg[j] = own[j];
+  auto put_total = [&](int seg) {
+    uint32_t c[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) c[j] = pr[j];
+    full_normalise<HG>(c, x);
+    if (keepA) {
+#pragma unroll
+      for (int j = 0; j < K; ++j) A.total[(inst * nseg + seg) * (size_t)L2 + x * K + j] = c[j];
+    }
+  };
 #pragma unroll 1
   for (int d = 2; d < tsize; ++d) {
     pairmul<H, K, false, true>(own, own, mreg, n, 0, halfB, selB);
+    if ((d & (seg_len - 1)) == 0) {     // a new segment starts: its running product is a_d itself
+      put_total(d / seg_len - 1);
+#pragma unroll
+      for (int j = 0; j < K; ++j) pr[j] = own[j];
+    } else {
+      uint32_t t[K];
+      montmul_reg<HG, false, false>(t, pr, own, nt, n0t);
+#pragma unroll
+      for (int j = 0; j < K; ++j) pr[j] = t[j];
+    }
     if (live) {
 #pragma unroll
       for (int j = 0; j < K; ++j) row[(size_t)d * LQ + j] = own[j];
     }
+    if (keepA) {
+#pragma unroll
+      for (int j = 0; j < K; ++j) pre[(size_t)d * L2 + j] = pr[j];
+    }
+  }
+  put_total(nseg - 1);
+}
+
+// The second pass of the unit-factor table (see hensel_fb_build_kernel): one group per inversion segment walks its seg_len
+// entries back, u = total^-1 * R * (-k) mod n from the host, and stores beta_d over b_d.  Only the true modulus n is involved:
+// two half-width Montgomery products per entry, half A's lanes running M(u_d, a_d) while half B's run M(u_d, p_(d-1)).
+// Groups beyond the last segment (the padding of the last wavefront) repeat the last segment's walk for the sake of uniform
+// control flow and store nothing; they may read entries the owning group is replacing at that moment -- what they compute is
+// discarded, so that is harmless.
+template <int H, int K>
+__global__ __launch_bounds__(kWGThreads, K <= 14 ? 2 : 1) void hensel_fb_unit_factor_kernel(HenselFbUnitArgs A) {
+  using HG = Geo<H, K>;
+  constexpr int GS = 2 * H, IPW = kWave / GS, L2 = H * K, LQ = 2 * H * K;
+  const int lane = threadIdx.x % kWave, wv = threadIdx.x / kWave;
+  const int grp = lane / GS, xg = lane % GS, x = xg % H;
+  const uint32_t halfB = (uint32_t)(xg / H);
+  const int tsize = 1 << A.w, seg_len = A.seg_len, nseg = tsize / seg_len;
+  const size_t nsegs = (size_t)A.nwin * nseg;
+  size_t seg = ((size_t)blockIdx.x * kWavesPerWG + wv) * IPW + grp;
+  const bool live = seg < nsegs;
+  if (!live) seg = nsegs - 1;
+  const size_t inst = seg / nseg;                                  // the table row
+  uint32_t* row = A.table + inst * (size_t)tsize * LQ + xg * K;
+  const uint32_t* pre = A.prefix + inst * (size_t)tsize * L2 + x * K;
+  uint32_t nt[K], u[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    nt[j] = A.n[x * K + j];
+    u[j] = A.uinit[seg * (size_t)L2 + x * K + j];
+  }
+  const uint32_t n0t = A.n0inv;
+  const int d0 = (int)(seg % nseg) * seg_len;
+#pragma unroll 1
+  for (int d = d0 + seg_len - 1; d >= d0; --d) {
+    uint32_t ent[K], r[K], be[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) ent[j] = row[(size_t)d * LQ + j];            // half A: a_d, half B: b_d
+    if (d > d0) {
+      uint32_t mult[K];
+#pragma unroll
+      for (int j = 0; j < K; ++j) mult[j] = halfB ? pre[(size_t)(d - 1) * L2 + j] : ent[j];
+      montmul_reg<HG, false, false>(r, u, mult, nt, n0t);                    // half A: u_(d-1), half B: ia
+    } else {
+#pragma unroll
+      for (int j = 0; j < K; ++j) r[j] = u[j];
+    }
+    montmul_reg<HG, false, false>(be, ent, r, nt, n0t);                      // half B: beta_d < 2n  (half A: unused)
+    full_normalise<HG>(be, x);
+    cond_sub_limbs<HG>(be, nt, x, lane);
+    if (live && halfB) {
+#pragma unroll
+      for (int j = 0; j < K; ++j) row[(size_t)d * LQ + j] = be[j];
+    }
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const uint32_t below = dpp_from_below<H>(r[j]);                        // half B takes half A's u_(d-1)
+      u[j] = halfB ? below : r[j];
+    }
   }
 }
 
-// DJN encrypt c = (1 + n*m) * hs^r mod n^2 (pub_key.cpp:51-64, 88-105) in split form: hs^r as nwin-1 pair products
-// of table entries, the exit product under the true modulus n by the pair (1, -m) = 1 + n*m, then back to a
-// full-width residue: for canonical a, b < n the pair is c = a + n*b (< n^2), one full-width Montgomery product in
-// the geometry Geo<2H,K> of the n^2 context (two for a Montgomery-form result).
+// DJN encrypt c = (1 + n*m) * hs^r mod n^2 (pub_key.cpp:51-64, 88-105) in split form on the unit-factor table
+// (hensel_fb_build_kernel): hs^r == (prod alpha_i) * (1 + n*S), S = sum beta_i -- nwin-1 pair products by (alpha_i, 0), two
+// half-width products each, the beta_i added limb-wise in half B's lanes (a carry round every second step: limbs below
+// 3 * 2^29) --, then times 1 + n*(m + S) as two half-width products under the true modulus n (pair_times_gm_limbs; m + S <
+// (nwin + 2) * n stays far below R, the Montgomery product reduces it).  Resident results leave as the pair; others go back to
+// a full-width residue: for canonical a, b < n the pair is c = a + n*b (< n^2), one full-width Montgomery product in
+// the geometry Geo<2H,K> of the n^2 context (two for a Montgomery-form result) -- pair_exit_store.
 template <int H, int K>
 __global__ __launch_bounds__(kWGThreads, K <= 14 ? 2 : 1) void hensel_fb_encrypt_kernel(HenselFbArgs A) {
   using HG = Geo<H, K>;
@@ -664,12 +798,13 @@ __global__ __launch_bounds__(kWGThreads, K <= 14 ? 2 : 1) void hensel_fb_encrypt
   auto& rows = rows_[wv];
   const int grp = lane / GS, xg = lane % GS, x = xg % H;
   const uint32_t halfB = (uint32_t)(xg / H);
+  const uint32_t maskB = 0u - halfB;
   uint32_t selB = xg == H ? 1u : 0u;
   asm("" : "+v"(selB));
   const size_t first_inst = ((size_t)blockIdx.x * kWavesPerWG + wv) * IPW;
   size_t inst = first_inst + grp;
   if (inst >= A.count) inst = A.count - 1;
-  uint32_t n[K], own[K], mreg[K], nxt[K];
+  uint32_t n[K], own[K], mreg[K], nxt[K], S[K];
 #pragma unroll
   for (int j = 0; j < K; ++j) n[j] = A.ctx.nhat[x * K + j];
   const int w = A.w, tsize = 1 << w;
@@ -684,26 +819,47 @@ __global__ __launch_bounds__(kWGThreads, K <= 14 ? 2 : 1) void hensel_fb_encrypt
   auto load_entry = [&](uint32_t (&dst)[K], int i) {   // (masked: the address stream does not depend on the digits of r)
     load_table_entry<K>(dst, A.table + (size_t)i * tsize * LQ + xg * K, digit(i), tsize, LQ, A.ct_gather != 0);
   };
-  load_entry(own, 0);
+  load_entry(own, 0);                                   // half A: alpha_0, half B: beta_0
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    S[j] = own[j] & maskB;
+    own[j] &= ~maskB;                                   // the accumulator starts as (alpha_0, 0)
+  }
   if (A.nwin > 1) load_entry(mreg, 1);
   // the entry of the next step is fetched before the product of this one (latency hidden)
 #pragma unroll 1
   for (int i = 1; i < A.nwin; ++i) {
     if (i + 1 < A.nwin) load_entry(nxt, i + 1);
-    pairmul<H, K, false, true>(own, own, mreg, n, 0, halfB, selB);
+    pairmul<H, K, false, true, true>(own, own, mreg, n, 0, halfB, selB);
+    uint32_t be[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) be[j] = mreg[j] & maskB;
+    if (i & 1) {
+#pragma unroll
+      for (int j = 0; j < K; ++j) S[j] += be[j];
+    } else {
+      add_normalise<HG>(S, be);
+    }
 #pragma unroll
     for (int j = 0; j < K; ++j) mreg[j] = nxt[j];
   }
+  // times 1 + n*(m + S): two half-width products under the true modulus, only b changes
+  stage_words<FG>(io, A.fm_words, A.fm_stride, 0, A.fm_nwords, first_inst, A.count, 1, lane);
+  wave_lds_sync();
+  {
+    uint32_t mv[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) mv[j] = limb_from_words(io[grp], x * K + j);
+    add_normalise<HG>(mv, S);                           // (half A: m alone, unused)
+    pair_times_gm_limbs<H, K>(own, A.ctx, mv, x, halfB);
+  }
   if (A.out_pair) {
-    // resident result: stay a pair.  hs^r * (1 + n*m): two half-width products (pair_times_gm), no way back to words.
-    stage_words<FG>(io, A.fm_words, A.fm_stride, 0, A.fm_nwords, first_inst, A.count, 1, lane);
-    wave_lds_sync();
-    pair_times_gm<H, K>(own, A.ctx, io[grp], x, halfB);
+    // resident result: stay a pair, no way back to words
     if (first_inst + grp < A.count) store_pair_row<K>(A.out_pair + inst * (size_t)LQ, own, xg);
     return;
   }
-  pair_exit_store<H, K>(own, A.ctx, A.full, true, A.fm_words, A.fm_stride, A.fm_nwords, A.out, A.out_stride, first_inst,
-                        A.count, bl, io, rows, lane, grp, xg, halfB, selB);
+  pair_exit_store<H, K>(own, A.ctx, A.full, false, nullptr, 0, 0, A.out, A.out_stride, first_inst, A.count, bl, io, rows,
+                        lane, grp, xg, halfB, selB);
 }
 
 // base[i]^exp[i] modulo n^2 in split form -- CT x PT (ciphertext.cpp:143-162: per-element exponents, fixed window) and

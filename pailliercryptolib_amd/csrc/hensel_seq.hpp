@@ -66,7 +66,8 @@ __device__ __forceinline__ void seq_a_blocks(uint64_t (&c0)[K], uint64_t (&c1)[K
 }
 
 // w = a*d + b*c + q: mc (= b, or 2b in a squaring) times the rows of c, md (= d) times the rows of a, the digits of A
-template <int G, int K, bool SQR, bool UNITQ, int S, bool QLDS = false>
+// (DZ: the right-hand operand is (c, 0) -- a fixed-base table entry in unit-factor form: the d*a product is not issued)
+template <int G, int K, bool SQR, bool UNITQ, int S, bool QLDS = false, bool DZ = false>
 __device__ __forceinline__ void seq_b_blocks(uint64_t (&c0)[K], uint64_t (&c1)[K], const uint32_t (&mc)[K],
                                              const uint32_t (&md)[K], const uint32_t (&a)[K], const uint32_t (&c)[K],
                                              const uint32_t (&n)[K], uint32_t n0inv, uint32_t (&qd)[QLDS ? 1 : G][K],
@@ -85,7 +86,7 @@ __device__ __forceinline__ void seq_b_blocks(uint64_t (&c0)[K], uint64_t (&c1)[K
         else c1[r + j - K] += p;
       }
     }
-    if constexpr (!SQR) {
+    if constexpr (!SQR && !DZ) {
 #pragma unroll
       for (int r = 0; r < K; ++r) row[r] = bcast_lane<G, S>(a[r]);
 #pragma unroll
@@ -105,19 +106,21 @@ __device__ __forceinline__ void seq_b_blocks(uint64_t (&c0)[K], uint64_t (&c1)[K
     } else {
       mont_reduce_rows_q<HG, UNITQ, 2>(c0, c1, n, n0inv, qd[S], sel0);
     }
-    seq_b_blocks<G, K, SQR, UNITQ, S + 1, QLDS>(c1, c0, mc, md, a, c, n, n0inv, qd, sel0, qs);
+    seq_b_blocks<G, K, SQR, UNITQ, S + 1, QLDS, DZ>(c1, c0, mc, md, a, c, n, n0inv, qd, sel0, qs);
   }
 }
 
 // (a, b) = (a, b) (x) (c, d): the Montgomery product of two pairs held in the same lanes (lazy: inputs < 8P -> outputs
 // < 2P).  A squaring passes c = a, d = b.
 // (QLDS, ts != null: the new a part waits in LDS -- kAbPad words of this LANE -- while the b part is computed: K registers)
-template <int G, int K, bool SQR, bool UNITQ, bool QLDS = false>
+// (DZ: d is zero and is not read -- two half-width products instead of three)
+template <int G, int K, bool SQR, bool UNITQ, bool QLDS = false, bool DZ = false>
 __device__ __forceinline__ void seq_pairmul(uint32_t (&a)[K], uint32_t (&b)[K], const uint32_t (&c)[K],
                                             const uint32_t (&d)[K], const uint32_t (&n)[K], uint32_t n0inv, uint32_t sel0,
                                             uint32_t* qs = nullptr, uint32_t* ts = nullptr) {
   static_assert(3 * K + 6 < 64, "a column receives 3K products (+ relaxed limbs): must stay below 2^64");
   static_assert(G % 2 == 0, "blocks alternate between the two accumulator sets and end in the first");
+  static_assert(!(SQR && DZ), "a squaring has no zero operand");
   using HG = Geo<G, K>;
   uint32_t qd[QLDS ? 1 : G][K];
   uint32_t t[K];
@@ -144,9 +147,9 @@ __device__ __forceinline__ void seq_pairmul(uint32_t (&a)[K], uint32_t (&b)[K], 
       c0[j] = 0;
       c1[j] = 0;
       mc[j] = SQR ? b[j] << 1 : b[j];
-      md[j] = SQR ? 0u : d[j];
+      md[j] = (SQR || DZ) ? 0u : d[j];
     }
-    seq_b_blocks<G, K, SQR, UNITQ, 0, QLDS>(c0, c1, mc, md, a, c, n, n0inv, qd, sel0, qs);
+    seq_b_blocks<G, K, SQR, UNITQ, 0, QLDS, DZ>(c0, c1, mc, md, a, c, n, n0inv, qd, sel0, qs);
     montmul_finish<HG>(b, c0);
   }
   if constexpr (QLDS) {
@@ -440,10 +443,13 @@ __global__ __launch_bounds__(kWGThreads, 2) void pair_mul_seq_kernel(PairOpsArgs
   }
 }
 
-// DJN encrypt of resident batches (hensel_fb_encrypt_kernel's pair-row exit) with both halves in the same lanes:
-// hs^r as nwin-1 general pair products of table entries -- every one of them a product in which the paired form
-// leaves half A idle for a third of its multiply-accumulates -- then (1 + n*m) as  b += (-k^-1 * m * a) mod n
-// (pair_times_gm without the hand-over between halves).  The table is the one hensel_fb_build_kernel wrote.
+// DJN encrypt of resident batches (hensel_fb_encrypt_kernel's pair-row exit) with both halves in the same lanes.
+// The table (hensel_fb_build_kernel) is in unit-factor form: entry g == alpha * (1 + n*beta) (mod n^2) is stored as
+// (alpha, beta), so hs^r == (prod alpha_i) * (1 + n * sum beta_i): nwin-1 pair products by (alpha_i, 0) -- two half-width
+// products each instead of three --, the beta_i added limb-wise, and the sum joins m in the exit the kernel has anyway:
+// (1 + n*(m + S)) as  b += (-k^-1 * (m + S) * a) mod n  (pair_times_gm without the hand-over between halves).
+// S needs no reduction of its own: S + m < (nwin + 2) * n < 2^-25 * R (R >= 2^37 * n for every split form,
+// capi_keys.inc: build_hensel_pub), and the Montgomery product by gm returns a value below 2n whatever S is below R.
 template <int G, int K, int MINW = 2>   // (MINW: as hensel_decrypt_seq_kernel)
 __global__ __launch_bounds__(kWGThreads, MINW) void hensel_fb_encrypt_seq_kernel(HenselFbArgs A) {
   using HG = Geo<G, K>;
@@ -485,21 +491,32 @@ __global__ __launch_bounds__(kWGThreads, MINW) void hensel_fb_encrypt_seq_kernel
     load_pair_row<K>(da, e, x);
     load_pair_row<K>(db, e + L2, x);
   };
-  load_entry(a, b, 0);
+  // S: the sum of the entries' beta parts (canonical limbs in the table), lazy: a carry round every second step keeps
+  // its limbs below 3 * 2^29.  The accumulator starts as (alpha_0, 0).
+  uint32_t S[K];
+  load_entry(a, S, 0);
+#pragma unroll
+  for (int j = 0; j < K; ++j) b[j] = 0;
   if (A.nwin > 1) load_entry(ma, mb, 1);
   // the entry of the next step is fetched before the product of this one (latency hidden)
 #pragma unroll 1
   for (int i = 1; i < A.nwin; ++i) {
     uint32_t na[K], nb[K];
     if (i + 1 < A.nwin) load_entry(na, nb, i + 1);
-    seq_pairmul<G, K, false, true, true>(a, b, ma, mb, n, 0, sel0, qs, ts);
+    seq_pairmul<G, K, false, true, true, true>(a, b, ma, mb, n, 0, sel0, qs, ts);   // (DZ: mb is not read)
+    if (i & 1) {
+#pragma unroll
+      for (int j = 0; j < K; ++j) S[j] += mb[j];
+    } else {
+      add_normalise<HG>(S, mb);
+    }
 #pragma unroll
     for (int j = 0; j < K; ++j) {
       ma[j] = na[j];
       mb[j] = nb[j];
     }
   }
-  // times 1 + n*m under the true modulus n:  b += montmul(montmul(m, gm), a)
+  // times 1 + n*(m + S) under the true modulus n:  b += montmul(montmul(m + S, gm), a)
   stage_words<HG>(io, A.fm_words, A.fm_stride, 0, A.fm_nwords, first_inst, A.count, 1, lane);
   wave_lds_sync();
   {
@@ -510,6 +527,7 @@ __global__ __launch_bounds__(kWGThreads, MINW) void hensel_fb_encrypt_seq_kernel
       ma[j] = A.ctx.gm[x * K + j];
       mv[j] = limb_from_words(io[grp], x * K + j);
     }
+    add_normalise<HG>(mv, S);
     montmul_reg<HG, false, false>(u, mv, ma, n, A.ctx.n0inv);
     montmul_reg<HG, false, false>(v, u, a, n, A.ctx.n0inv);
     add_normalise<HG>(b, v);

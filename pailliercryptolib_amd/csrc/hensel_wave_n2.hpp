@@ -45,8 +45,10 @@ __device__ __forceinline__ void wvn_finish(uint32_t (&r)[LPL], const uint64_t (&
 // (a, b) = (a, b) (x) (cm, dm), or the square (SQR: cm = a, dm = b): t = a*cm with its digits; b = a*dm + b*cm + q reduced; the
 // two scans in lock-step and in the pinned order of hensel_wave.hpp: wv_pairop (its comment names the steps), every step on
 // LPL limbs.  The slide by one limb: limb j <- low(limb j+1) + high(limb j); the lane's top limb takes the next lane's limb 0.
+// DZ: dm is zero (a fixed-base table entry in unit-factor form, hensel.hpp: hensel_fb_build_kernel) and is not read: step A2 has
+// only its b*cm half.
 #define WV_PIN __builtin_amdgcn_sched_barrier(0)
-template <int L2, int LPL, int LB, bool SQR, bool WIDEQ>
+template <int L2, int LPL, int LB, bool SQR, bool WIDEQ, bool DZ = false>
 __device__ __forceinline__ void wvn_pairop(uint32_t (&a)[LPL], uint32_t (&b)[LPL], const uint32_t (&cm)[LPL],
                                            const uint32_t (&dm)[LPL], const WaveCtxN<LPL>& c) {
   uint64_t acc1[LPL], acc2[LPL];
@@ -57,7 +59,7 @@ __device__ __forceinline__ void wvn_pairop(uint32_t (&a)[LPL], uint32_t (&b)[LPL
     a0[j] = a[j];
     b0[j] = b[j];
     m1[j] = SQR ? a[j] : cm[j];
-    m2[j] = SQR ? b[j] << 1 : dm[j];
+    m2[j] = SQR ? b[j] << 1 : (DZ ? 0u : dm[j]);
     lo1[j] = lo2[j] = 0;
   }
   uint32_t sa[L2 + 2], sb[L2 + 2];                               // the limbs of a (and b) as SGPRs, fetched two steps ahead
@@ -91,9 +93,11 @@ __device__ __forceinline__ void wvn_pairop(uint32_t (&a)[LPL], uint32_t (&b)[LPL
       asm volatile("" : "+v"(acc2[0]) : "s"(q1));
       WV_PIN;
     }
+    if constexpr (!DZ) {
 #pragma unroll
-    for (int j = 0; j < LPL; ++j) wv_mac(acc2[j], sa[i], m2[j]);                                   // A2
-    WV_PIN;
+      for (int j = 0; j < LPL; ++j) wv_mac(acc2[j], sa[i], m2[j]);                                 // A2
+      WV_PIN;
+    }
     if constexpr (!SQR) {
 #pragma unroll
       for (int j = 0; j < LPL; ++j) wv_mac(acc2[j], sb[i], m1[j]);
@@ -309,8 +313,11 @@ __device__ __forceinline__ void wvn_montmul_true(uint32_t (&r)[LPL], const uint3
 
 // DJN encrypt of small batches on the fixed-base table of pairs (hensel.hpp: hensel_fb_encrypt_kernel; PublicKey::encrypt,
 // ipcl/pub_key.cpp:51-64, 88-105): ONE wavefront per element.  hs^r = the product of one table entry per w-bit digit of r --
-// nwin - 1 pair products, the entry of the next step fetched while this one's product runs --, then times g^m = 1 + n*m as
-// two half-width products under the true modulus n (hensel.hpp: pair_times_gm: only b changes, b += (-k^-1 m a) mod n);
+// nwin - 1 pair products, the entry of the next step fetched while this one's product runs.  The table is in unit-factor form
+// (hensel.hpp: hensel_fb_build_kernel): an entry is (alpha, beta) with g == alpha * (1 + n*beta) mod n^2, the products run by
+// (alpha, 0) (wvn_pairop<.., DZ>), the betas are summed limb-wise (one carry round per step) and the sum S joins the plaintext:
+// times 1 + n*(m + S) as two half-width products under the true modulus n (hensel.hpp: pair_times_gm: only b changes,
+// b += (-k^-1 (m + S) a) mod n; m + S < (nwin + 2) n is far below R, the Montgomery product reduces it);
 // the result leaves as a pair row (A.out_pair).  The last pair product runs with masked digits (rows below 2 P).
 template <int L2, int LPL, bool WIDEQ>
 __global__ __launch_bounds__(kWGThreads, 1) void hensel_fb_encrypt_wave_kernel(HenselFbArgs A) {
@@ -368,20 +375,39 @@ __global__ __launch_bounds__(kWGThreads, 1) void hensel_fb_encrypt_wave_kernel(H
       }
     }
   };
-  uint32_t a[LPL], b[LPL], ma[LPL], mb[LPL], na[LPL], nb[LPL];
-  load_entry(a, b, 0);
+  uint32_t a[LPL], b[LPL], ma[LPL], mb[LPL], na[LPL], nb[LPL], S[LPL];
+  // S += y, one carry round: canonical y, limbs of S back below 2^29 + 2
+  auto sum_beta = [&](const uint32_t (&y)[LPL]) {
+    uint32_t cy[LPL];
+#pragma unroll
+    for (int j = 0; j < LPL; ++j) {
+      S[j] += y[j];
+      cy[j] = S[j] >> LB;
+      S[j] &= c.maskv;
+    }
+    S[0] += wv_up(cy[LPL - 1]);
+#pragma unroll
+    for (int j = 1; j < LPL; ++j) S[j] += cy[j - 1];
+  };
+  load_entry(a, S, 0);                              // the accumulator starts as (alpha_0, 0), the sum as beta_0
+#pragma unroll
+  for (int j = 0; j < LPL; ++j) b[j] = 0;
   if (A.nwin > 1) load_entry(ma, mb, 1);
 #pragma unroll 1
   for (int i = 1; i + 1 < A.nwin; ++i) {
     load_entry(na, nb, i + 1);                      // (in flight while the product runs)
-    wvn_pairop<L2, LPL, LB, false, WIDEQ>(a, b, ma, mb, c);
+    wvn_pairop<L2, LPL, LB, false, WIDEQ, true>(a, b, ma, mb, c);
+    sum_beta(mb);
 #pragma unroll
     for (int j = 0; j < LPL; ++j) {
       ma[j] = na[j];
       mb[j] = nb[j];
     }
   }
-  if (A.nwin > 1) wvn_pairop<L2, LPL, LB, false, false>(a, b, ma, mb, c);
+  if (A.nwin > 1) {
+    wvn_pairop<L2, LPL, LB, false, false, true>(a, b, ma, mb, c);
+    sum_beta(mb);
+  }
   // ---- times g^m: b += (-k^-1 m a) mod n, two products under the true modulus ----
   {
     uint32_t nt[LPL], gm[LPL], mv[LPL], u[LPL], v[LPL];
@@ -395,7 +421,8 @@ __global__ __launch_bounds__(kWGThreads, 1) void hensel_fb_encrypt_wave_kernel(H
       if (in && sh > 64 - LB && word + 1 < A.fm_nwords) val |= mw[word + 1] << (64 - sh);
       mv[j] = (uint32_t)val & c.maskv;
     }
-    wvn_montmul_true<L2, LPL, LB>(u, mv, gm, nt, A.ctx.n0inv, c.maskv, c.onev);
+    sum_beta(mv);                                   // S = m + sum of the betas
+    wvn_montmul_true<L2, LPL, LB>(u, S, gm, nt, A.ctx.n0inv, c.maskv, c.onev);
     wvn_montmul_true<L2, LPL, LB>(v, u, a, nt, A.ctx.n0inv, c.maskv, c.onev);
     // b += v, then one carry round: limbs back below 2^29 + 2 (what the readers of pair rows are sized for)
     uint32_t cy[LPL];

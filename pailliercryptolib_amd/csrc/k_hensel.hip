@@ -66,6 +66,13 @@ bool PGPU_FB_NAME(launch_hensel_fb_build)(int H, int K, const HenselFbBuildArgs&
   }
   return false;
 }
+bool PGPU_FB_NAME(launch_hensel_fb_unit_factor)(int H, int K, const HenselFbUnitArgs& a, unsigned blocks, hipStream_t s) {
+  if (H == PGPU_FB_H && K == PGPU_FB_K) {
+    hipLaunchKernelGGL((hensel_fb_unit_factor_kernel<PGPU_FB_H, PGPU_FB_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
+    return true;
+  }
+  return false;
+}
 bool PGPU_FB_NAME(launch_hensel_fb_encrypt)(int H, int K, const HenselFbArgs& a, unsigned blocks, hipStream_t s) {
   if (H == PGPU_FB_H && K == PGPU_FB_K) {
     hipLaunchKernelGGL((hensel_fb_encrypt_kernel<PGPU_FB_H, PGPU_FB_K>), dim3(blocks), dim3(kWGThreads), PGPU_PLACE_PAD((hensel_fb_encrypt_kernel<PGPU_FB_H, PGPU_FB_K>), blocks), s, a);

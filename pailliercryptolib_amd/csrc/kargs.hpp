@@ -193,9 +193,25 @@ struct HenselFbBuildArgs {
   int base_words;
   int chunk_words;
   int nchunks;
-  uint32_t* table;       // [nwin][2^w] pairs
+  uint32_t* table;       // [nwin][2^w] entries of 2*L2 limbs: pairs (a, b); hensel_fb_unit_factor_kernel then makes them (alpha, beta)
   int nwin;
   int w;
+  // unit-factor form (hensel.hpp: hensel_fb_unit_factor_kernel follows): the running products of the a parts under the true modulus
+  int seg_len;           // entries per inversion segment: a power of two, 2 <= seg_len <= 2^w; nseg = 2^w / seg_len per row
+  uint32_t* prefix;      // [nwin][2^w][L2] scratch out: running products of the a parts, M(x, y) = x*y*R^-1 mod n, restarted per segment
+  uint32_t* total;       // [nwin][nseg][L2] out: the last running product of each segment, canonical limbs
+};
+
+// Second pass over a table hensel_fb_build_kernel wrote: every b part is replaced by beta (hensel.hpp: hensel_fb_unit_factor_kernel).
+struct HenselFbUnitArgs {
+  const uint32_t* n;     // [L2] the true modulus n
+  uint32_t n0inv;        // -n^-1 mod 2^29
+  uint32_t* table;       // [nwin][2^w] entries of 2*L2 limbs: (a, b) in, (a, beta) out
+  int nwin;
+  int w;
+  int seg_len;           // as HenselFbBuildArgs
+  const uint32_t* prefix;   // [nwin][2^w][L2] the running products phase one left
+  const uint32_t* uinit;    // [nwin][nseg][L2] per segment: total^-1 * R * (-k) mod n, from the host
 };
 
 // The way back from a canonical pair (a, b), a, b < n, to the full-width residue c = a + n*b modulo n^2, in the
@@ -212,7 +228,7 @@ struct HenselFullDev {
 struct HenselFbArgs {
   HenselPubDev ctx;
   HenselFullDev full;
-  const uint32_t* table;     // [nwin][2^w] pairs
+  const uint32_t* table;     // [nwin][2^w] unit-factor entries (alpha, beta): g == alpha * (1 + n*beta) mod n^2, beta canonical
   int nwin;
   int w;
   const uint64_t* exp;       // [count][exp_stride] the randomness r

@@ -141,6 +141,10 @@ bool launch_hensel_fb_build_part3(int H, int K, const HenselFbBuildArgs& a, unsi
 bool launch_hensel_fb_build_part4(int H, int K, const HenselFbBuildArgs& a, unsigned blocks, hipStream_t s);
 bool launch_hensel_fb_build_part10(int H, int K, const HenselFbBuildArgs& a, unsigned blocks, hipStream_t s);
 bool launch_hensel_fb_build_part22(int H, int K, const HenselFbBuildArgs& a, unsigned blocks, hipStream_t s);
+bool launch_hensel_fb_unit_factor_part3(int H, int K, const HenselFbUnitArgs& a, unsigned blocks, hipStream_t s);
+bool launch_hensel_fb_unit_factor_part4(int H, int K, const HenselFbUnitArgs& a, unsigned blocks, hipStream_t s);
+bool launch_hensel_fb_unit_factor_part10(int H, int K, const HenselFbUnitArgs& a, unsigned blocks, hipStream_t s);
+bool launch_hensel_fb_unit_factor_part22(int H, int K, const HenselFbUnitArgs& a, unsigned blocks, hipStream_t s);
 bool launch_hensel_fb_encrypt_part22(int H, int K, const HenselFbArgs& a, unsigned blocks, hipStream_t s);
 bool launch_hensel_fb_encrypt_part3(int H, int K, const HenselFbArgs& a, unsigned blocks, hipStream_t s);
 bool launch_hensel_fb_encrypt_part4(int H, int K, const HenselFbArgs& a, unsigned blocks, hipStream_t s);
@@ -150,6 +154,15 @@ inline bool launch_hensel_fb_build(int H, int K, const HenselFbBuildArgs& a, uns
          launch_hensel_fb_build_part10(H, K, a, blocks, s)
 #if PGPU_WITH_4096
          || launch_hensel_fb_build_part22(H, K, a, blocks, s)
+#endif
+      ;
+}
+// the second pass of the table build (hensel.hpp: hensel_fb_unit_factor_kernel): one group per inversion segment
+inline bool launch_hensel_fb_unit_factor(int H, int K, const HenselFbUnitArgs& a, unsigned blocks, hipStream_t s) {
+  return launch_hensel_fb_unit_factor_part3(H, K, a, blocks, s) || launch_hensel_fb_unit_factor_part4(H, K, a, blocks, s) ||
+         launch_hensel_fb_unit_factor_part10(H, K, a, blocks, s)
+#if PGPU_WITH_4096
+         || launch_hensel_fb_unit_factor_part22(H, K, a, blocks, s)
 #endif
       ;
 }
