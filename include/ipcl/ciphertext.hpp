@@ -14,6 +14,8 @@ namespace ipcl {
 class CipherText;
 namespace ext {   // include/ipcl/ext/linear.hpp
 CipherText matVec(const PlainText& w, std::size_t rows, const CipherText& x);
+// include/ipcl/ext/aggregate.hpp
+CipherText segmentSum(const CipherText& x, const std::vector<uint32_t>& ids, std::size_t n_segments, std::size_t groups);
 }
 
 class CipherText : public BaseText {
@@ -42,6 +44,10 @@ class CipherText : public BaseText {
   friend class PublicKey;
   friend CipherText ext::matVec(const PlainText& w, std::size_t rows, const CipherText& x);
   CipherText linearMap(const PlainText& w, std::size_t rows) const;   // prod_j this[j]^w[i][j]: csrc/host/linear.cpp
+  friend CipherText ext::segmentSum(const CipherText& x, const std::vector<uint32_t>& ids, std::size_t n_segments,
+                                    std::size_t groups);
+  // prod_{j: ids[g][j] == s} this[j]: csrc/host/aggregate.cpp
+  CipherText segmentMap(const std::vector<uint32_t>& ids, std::size_t n_segments, std::size_t groups) const;
   CipherText(const PublicKey& pk, std::shared_ptr<detail::DeviceBatch> dev);
   CipherText(std::shared_ptr<PublicKey> pk, std::shared_ptr<detail::DeviceBatch> dev);
   std::shared_ptr<PublicKey> m_pk;

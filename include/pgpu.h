@@ -321,6 +321,32 @@ int pgpu_batch_ct_matvec(const pgpu_pubkey* key, const pgpu_batch* x, const pgpu
  * afterwards) and the bytes of the shared window table (cols * 2^window pair rows).  The rule is policy.hpp: matvec_*;
  * PGPU_MATVEC_WINDOW / PGPU_MATVEC_SLICES force the two values.  PGPU_ERR_UNSUPPORTED: no pair rows for keys of key_bits. */
 int pgpu_ct_matvec_plan(int key_bits, size_t rows, size_t cols, int e_bits, int* window, int* slices, size_t* table_bytes);
+/* Encrypted segmented sum (a histogram, a per-key aggregate, a pooling step): x a resident ciphertext batch of
+ * cols = pgpu_batch_count(x) elements (pair rows, or uploaded plain ciphertext words: converted on the way in), ids a HOST
+ * array of groups*cols segment numbers, row-major:
+ *     out[g*n_segments + s] = prod_{ j : ids[g*cols + j] == s } x[j] mod n^2     i.e. Dec(out[g][s]) = sum of those Dec(x[j]) mod n
+ * groups > 1: the same x under several groupings (one histogram per feature over the same samples).  An id equal to
+ * PGPU_SEGMENT_NONE leaves the element out of that group; an empty segment yields the ciphertext 1, as an all-zero matrix
+ * row does in pgpu_batch_ct_matvec.  The host sorts the element numbers by segment, cuts every segment into chunks (one
+ * product chain each) and folds the partial products of long segments level by level with the same kernel (DESIGN.md:
+ * "Encrypted segmented sum").  The result is an ordinary resident ciphertext batch of groups*n_segments elements on the
+ * lane of x; ids may be reused as soon as the call returns.
+ * PGPU_ERR_INVALID_PARAM: null / stale handles, groups == 0, n_segments == 0, ciphertext width mismatch, a batch of another
+ * key, an id >= n_segments other than PGPU_SEGMENT_NONE, groups*cols or groups*n_segments beyond what the call addresses.
+ * PGPU_ERR_UNSUPPORTED: keys without pair rows (beyond 3072 bits; PGPU_PAIR_ROWS=0 / PGPU_HENSEL=0), pools of more than one
+ * GPU, and -- SIDE CHANNELS -- the masked table-gather policy: the rows of x are addressed by the caller's PLAINTEXT ids
+ * (never by key material or by anything encrypted), which is the indexed access of the default policy; with
+ * pgpu_set_table_gather_policy(1) the call is refused rather than run with an access pattern the policy excludes.
+ * All refusals are decided on the host before any launch and leave *out untouched. */
+#define PGPU_SEGMENT_NONE 0xFFFFFFFFu
+int pgpu_batch_ct_segment_sum(const pgpu_pubkey* key, const pgpu_batch* x, const uint32_t* ids, size_t groups,
+                              size_t n_segments, pgpu_batch** out);
+/* What a call of this shape would run (host-side query, needs no device): elements = the ids that are not
+ * PGPU_SEGMENT_NONE, segments = groups * n_segments, longest_segment = the elements of the fullest segment.  chunk: the
+ * entries one product chain multiplies; levels: the launches, ceil(log_chunk(longest_segment)), at least 1.  The rule is
+ * policy.hpp: segsum_*; PGPU_SEGSUM_CHUNK=c (c >= 2) forces the chunk.
+ * PGPU_ERR_UNSUPPORTED: no pair rows for keys of key_bits. */
+int pgpu_ct_segment_sum_plan(int key_bits, size_t elements, size_t segments, size_t longest_segment, int* chunk, int* levels);
 
 /* ---- instrumentation used by bench.py (roofline) ----
  * With timing enabled every kernel launch is bracketed by two HIP events recorded on the stream
@@ -332,7 +358,8 @@ typedef enum pgpu_kernel_kind {
   PGPU_KERNEL_MODMUL = 2,     /* modmul_kernel */
   PGPU_KERNEL_CRT = 3,        /* crt_kernel (decrypt stage 2) */
   PGPU_KERNEL_FB_ENCRYPT = 4, /* fb_encrypt_kernel (DJN encrypt, fixed-base) */
-  PGPU_KERNEL_MATVEC = 5      /* every launch of pgpu_batch_ct_matvec: table build, multi-exponentiation, fold */
+  PGPU_KERNEL_MATVEC = 5,     /* every launch of pgpu_batch_ct_matvec: table build, multi-exponentiation, fold */
+  PGPU_KERNEL_SEGSUM = 6      /* every launch of pgpu_batch_ct_segment_sum: one per level */
 } pgpu_kernel_kind;
 int pgpu_set_timing(int enabled);
 int pgpu_timing_collect(int* kinds, double* ms, int max_entries);

@@ -36,8 +36,10 @@ SYMBOLS = [
     "pgpu_encrypt_kernel_form_ex", "pgpu_host_alloc", "pgpu_host_free", "pgpu_host_wait",
     "pgpu_timing_collect_trace",
     "pgpu_batch_ct_matvec", "pgpu_ct_matvec_plan",
+    "pgpu_batch_ct_segment_sum", "pgpu_ct_segment_sum_plan",
 ]
 FEATURE_4096_SPLIT = 1
+SEGMENT_NONE = 0xFFFFFFFF      # PGPU_SEGMENT_NONE: the element is left out of that group
 
 _lib = None
 
@@ -169,6 +171,10 @@ def lib():
     L.pgpu_batch_ct_matvec.restype = c_int
     L.pgpu_ct_matvec_plan.argtypes = [c_int, c_size_t, c_size_t, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_size_t)]
     L.pgpu_ct_matvec_plan.restype = c_int
+    L.pgpu_batch_ct_segment_sum.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, POINTER(c_void_p)]
+    L.pgpu_batch_ct_segment_sum.restype = c_int
+    L.pgpu_ct_segment_sum_plan.argtypes = [c_int, c_size_t, c_size_t, c_size_t, POINTER(c_int), POINTER(c_int)]
+    L.pgpu_ct_segment_sum_plan.restype = c_int
     _lib = L
     return L
 

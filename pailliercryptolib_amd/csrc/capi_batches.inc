@@ -682,6 +682,129 @@ int pgpu_batch_ct_matvec(const pgpu_pubkey* key, const pgpu_batch* x, const pgpu
   return PGPU_OK;
 }
 
+// ---- encrypted segmented sum (hensel_segsum.hpp; policy.hpp: segsum_*) ----
+int pgpu_ct_segment_sum_plan(int key_bits, size_t elements, size_t segments, size_t longest_segment, int* chunk, int* levels) {
+  if (key_bits < 1 || segments == 0 || longest_segment > elements)
+    return fail(PGPU_ERR_INVALID_PARAM, "segment sum plan: key_bits and segments must be positive, longest_segment at most elements");
+  int G = 0, K = 0;
+  if (!policy::matvec_geometry(key_bits, &G, &K))
+    return fail(PGPU_ERR_UNSUPPORTED, "segment sum: keys of this size have no pair rows (1024- to 3072-bit key classes only)");
+  const int c = policy::segsum_chunk(G, elements);
+  if (chunk) *chunk = c;
+  if (levels) *levels = policy::segsum_levels(c, longest_segment);
+  return PGPU_OK;
+}
+
+int pgpu_batch_ct_segment_sum(const pgpu_pubkey* key, const pgpu_batch* x, const uint32_t* ids, size_t groups,
+                              size_t n_segments, pgpu_batch** out) {
+  RC_TRY(rt::check_ready());
+  if (!key || !x || !ids || !out) return fail(PGPU_ERR_INVALID_PARAM, "null argument");
+  RC_TRY(check_gen(key->gen, "key"));
+  RC_TRY(check_gen(x->gen, "batch"));
+  const int W = 2 * key->n_words;
+  const size_t cols = x->count;
+  if (groups == 0 || n_segments == 0) return fail(PGPU_ERR_INVALID_PARAM, "segment sum error: groups and n_segments must be positive");
+  if (x->words != W) return fail(PGPU_ERR_INVALID_PARAM, "segment sum error: ciphertext width mismatch");
+  // (element numbers are 32-bit entries of the sorted list, segment and partial-row numbers 31-bit fields of a descriptor)
+  constexpr size_t kMax = (size_t)1 << 31;
+  if (cols >= kMax || groups >= kMax / cols || n_segments >= kMax / groups)
+    return fail(PGPU_ERR_INVALID_PARAM, "segment sum error: groups * count(x) and groups * n_segments must stay below 2^31");
+  if (!same_domain(x->mont, key->nsq)) return fail(PGPU_ERR_INVALID_PARAM, "segment sum error: batch belongs to a different key");
+  if (rt::pool_size() > 1)
+    return fail(PGPU_ERR_UNSUPPORTED, "segment sum: pools of more than one GPU are not supported (segments are not sharded yet)");
+  const pgpu_pubkey::PubForm* pf = pair_form(key);
+  if (!pf || !pgpu::matvec_has(pf->H, pf->K))
+    return fail(PGPU_ERR_UNSUPPORTED, "segment sum: key has no pair form (1024- to 3072-bit keys; PGPU_PAIR_ROWS=0 / PGPU_HENSEL=0 switch it off)");
+  // the rows of x are addressed by the caller's plaintext ids: indexed access.  Under the masked policy the call is refused
+  // rather than quietly breaking that promise.
+  if (g_ct_gather.load())
+    return fail(PGPU_ERR_UNSUPPORTED, "segment sum: the masked table-gather policy is on (pgpu_set_table_gather_policy / PGPU_CT_GATHER) and "
+                                      "this call addresses the ciphertext rows by the plaintext segment ids; no masked variant exists");
+  if (x->pair_l2 && (x->pair_l2 != pf->H * pf->K || !(x->pair_form->n == key->n)))
+    return fail(PGPU_ERR_INVALID_PARAM, "segment sum error: batch belongs to a different key");
+  // the plan, on the host: sorted element numbers, chunk descriptors level by level
+  const int G = pf->H, K = pf->K, l2 = G * K;
+  const size_t LQ = (size_t)2 * l2, row_bytes = LQ * sizeof(uint32_t), segments = groups * n_segments;
+  std::vector<uint32_t> perm;
+  std::vector<size_t> offsets;
+  if (!policy::segsum_sort(ids, groups, cols, n_segments, &perm, &offsets))
+    return fail(PGPU_ERR_INVALID_PARAM, "segment sum error: a segment id is neither below n_segments nor PGPU_SEGMENT_NONE");
+  policy::SegsumPlan plan;
+  policy::segsum_plan(offsets, policy::segsum_chunk(G, perm.size()), &plan);
+  // one image for the device: the sorted list (never empty: the kernel reads entry 0 for the groups past their end), then
+  // the descriptors of every level
+  const size_t perm_bytes = (std::max<size_t>(1, perm.size()) * sizeof(uint32_t) + 15) & ~(size_t)15;
+  // partial rows: level l reads what level l - 1 wrote, so two regions serve all levels in turn
+  size_t image_bytes = perm_bytes, region[2] = {0, 0};
+  for (size_t l = 0; l < plan.levels.size(); ++l) {
+    image_bytes += plan.levels[l].chunks.size() * sizeof(pgpu::SegsumChunk);
+    region[l & 1] = std::max(region[l & 1], plan.levels[l].partial_rows);
+  }
+  std::vector<char> image(image_bytes, 0);
+  if (!perm.empty()) std::memcpy(image.data(), perm.data(), perm.size() * sizeof(uint32_t));
+  {
+    size_t at = perm_bytes;
+    for (const auto& lv : plan.levels) {
+      std::memcpy(image.data() + at, lv.chunks.data(), lv.chunks.size() * sizeof(pgpu::SegsumChunk));
+      at += lv.chunks.size() * sizeof(pgpu::SegsumChunk);
+    }
+  }
+  std::unique_ptr<pgpu_batch> tx;
+  RC_TRY(as_pair_batch(key, x, &x, &tx));
+  std::unique_ptr<pgpu_batch> o;
+  RC_TRY(new_batch(segments, W, &o, l2, x->lane));
+  o->pair_form = pair_form_shared(key);
+  rt::Device& dev = rt::device(0);
+  rt::DeviceGuard g(dev.ordinal);
+  hipStream_t s = dev.bs(x->lane);
+  // plan image and partial rows: the block arena, on the lane's stream like the operands themselves -- what the arena hands
+  // out again it hands to this stream, behind the kernels below
+  rt::DevMem dimage, partial;
+  RC_TRY(dimage.alloc(dev, s, image_bytes));
+  if (region[0]) RC_TRY(partial.alloc(dev, s, (region[0] + region[1]) * row_bytes));
+  if (image_bytes <= kBounceBytes) {
+    Bounce& bn = bounce();
+    RC_TRY(bn.ready());
+    std::memcpy(bn.p, image.data(), image_bytes);
+    HIP_TRY(hipMemcpyAsync(dimage.p, bn.p, image_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(bn.ev, s));
+    bn.pending = true;
+  } else {   // through a worker lane's staging buffers, queued on the same stream: nothing is waited for
+    rt::TaskGroup tg;
+    void* dst = dimage.p;
+    const char* src = image.data();
+    tg.run(dev, [=](rt::Lane& lane) -> int { return lane.h2d(dst, src, image_bytes, s); });
+    RC_TRY(tg.wait());
+  }
+  // the form with the same limbs per half on more lanes, for the levels that leave SIMDs empty (2048-bit keys: (8,9))
+  const pgpu_pubkey::PubForm* wide = nullptr;
+  for (const auto& alt : key->hforms)
+    if (alt->H * alt->K == l2 && alt->H > G && pgpu::segsum_wide_has(alt->H, alt->K)) wide = alt.get();
+  pgpu::SegsumArgs a{};
+  a.out = o->prow(0);
+  uint32_t* const reg[2] = {(uint32_t*)partial.p, partial.p ? (uint32_t*)partial.p + region[0] * LQ : nullptr};
+  size_t at = perm_bytes;
+  for (size_t l = 0; l < plan.levels.size(); ++l) {
+    const auto& lv = plan.levels[l];
+    const pgpu_pubkey::PubForm* lf = wide && policy::segsum_wide_pays(wide->H, lv.chunks.size()) ? wide : pf;
+    a.ctx = hensel_pub_view(lf, dev.index);
+    a.src = l == 0 ? x->prow(0) : reg[(l - 1) & 1];
+    a.perm = l == 0 ? (const uint32_t*)dimage.p : nullptr;
+    a.chunks = (const pgpu::SegsumChunk*)((const char*)dimage.p + at);
+    a.n_chunks = lv.chunks.size();
+    a.partial = reg[l & 1];
+    const size_t ipw = 64 / (size_t)lf->H, waves = (a.n_chunks + ipw - 1) / ipw;
+    TimerScope t(dev, s, PGPU_KERNEL_SEGSUM, PGPU_FORM_SEQ);
+    if (!pgpu::launch_segsum(lf->H, lf->K, a, (unsigned)((waves + pgpu::kWavesPerWG - 1) / pgpu::kWavesPerWG), s))
+      return fail(PGPU_ERR_UNSUPPORTED, "segment sum kernels not compiled for this key class");
+    HIP_TRY(hipGetLastError());
+    t.stop();
+    at += lv.chunks.size() * sizeof(pgpu::SegsumChunk);
+  }
+  *out = o.release();
+  return PGPU_OK;
+}
+
 int pgpu_set_batch_lane(int lane) {
   if (lane < 0 || lane >= rt::kBatchLanes) return fail(PGPU_ERR_INVALID_PARAM, "batch lane out of range (pgpu_batch_lanes())");
   t_batch_lane = lane;

@@ -1,5 +1,5 @@
 // pailliercryptolib_amd -- instantiations of the split-form CRT-decrypt exponentiation (hensel.hpp), split over
-// PGPU_PART = 0..40 so that they compile in parallel (38-40: the encrypted matrix-vector product; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
+// PGPU_PART = 0..44 so that they compile in parallel (38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
 // the two-wavefronts-per-SIMD build of the (2,19) decrypt form; 11-13: element-wise operations on pair rows).
 #include "hensel_seq.hpp"
 #include "launch.hpp"
@@ -15,9 +15,12 @@
 #if defined(PGPU_PART) && PGPU_PART >= 38 && PGPU_PART <= 40
 #include "hensel_matvec.hpp"    // the encrypted matrix-vector product: shared window tables + multi-exponentiation
 #endif
+#if defined(PGPU_PART) && PGPU_PART >= 41 && PGPU_PART <= 44
+#include "hensel_segsum.hpp"    // the encrypted segmented sum: one product chain per chunk of a sorted index list
+#endif
 
 #ifndef PGPU_PART
-#error "compile with -DPGPU_PART=0..40 (15 and 30 are retired)"
+#error "compile with -DPGPU_PART=0..44 (15 and 30 are retired)"
 #endif
 
 namespace pgpu {
@@ -456,6 +459,30 @@ bool PGPU_MV_NAME(int G, int K, bool table, const MatvecArgs& a, unsigned blocks
   if (G != PGPU_MV_G || K != PGPU_MV_K) return false;
   if (table) hipLaunchKernelGGL((matvec_table_kernel<PGPU_MV_G, PGPU_MV_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
   else hipLaunchKernelGGL((matvec_kernel<PGPU_MV_G, PGPU_MV_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
+  return true;
+}
+#elif PGPU_PART >= 41 && PGPU_PART <= 44
+// the encrypted segmented sum (hensel_segsum.hpp): one geometry per part
+#if PGPU_PART == 41
+#define PGPU_SS_G 4
+#define PGPU_SS_K 18
+#define PGPU_SS_NAME launch_segsum_part41
+#elif PGPU_PART == 42
+#define PGPU_SS_G 8
+#define PGPU_SS_K 14
+#define PGPU_SS_NAME launch_segsum_part42
+#elif PGPU_PART == 43
+#define PGPU_SS_G 2
+#define PGPU_SS_K 19
+#define PGPU_SS_NAME launch_segsum_part43
+#else
+#define PGPU_SS_G 8
+#define PGPU_SS_K 9
+#define PGPU_SS_NAME launch_segsum_part44
+#endif
+bool PGPU_SS_NAME(int G, int K, const SegsumArgs& a, unsigned blocks, hipStream_t s) {
+  if (G != PGPU_SS_G || K != PGPU_SS_K) return false;
+  hipLaunchKernelGGL((segsum_kernel<PGPU_SS_G, PGPU_SS_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
   return true;
 }
 #else

@@ -314,6 +314,25 @@ struct MatvecArgs {
   uint32_t* out;             // [slices][rows][2*L2] partial products as pair rows (matvec_kernel)
 };
 
+// Encrypted segmented sum on pair rows (hensel_segsum.hpp): one product chain per chunk descriptor.  A chunk multiplies the
+// rows src[perm[begin]], ..., src[perm[begin + len - 1]] (perm == null: src[begin + i]) and writes one row: dst with
+// kSegsumPartial set names a row of `partial` (the input of the next level), without it a row of `out`.
+struct SegsumChunk {
+  uint64_t begin;            // first entry of perm (level 0) / first row of src (fold levels)
+  uint32_t len;              // 0: an empty segment, the row of one
+  uint32_t dst;
+};
+constexpr uint32_t kSegsumPartial = 0x80000000u;
+struct SegsumArgs {
+  HenselPubDev ctx;
+  const uint32_t* src;       // [..][2*L2] pair rows: the ciphertexts (level 0) or the partial rows of the level before
+  const uint32_t* perm;      // element numbers ordered by segment, or null: the identity (fold levels)
+  const SegsumChunk* chunks; // [n_chunks], ordered by len descending: the chunks of a wavefront are nearly equally long
+  size_t n_chunks;           // >= 1
+  uint32_t* out;             // [segments][2*L2] the result batch
+  uint32_t* partial;         // [..][2*L2] partial rows this level writes
+};
+
 struct FixedBaseArgs {
   ModCtxDev ctx;         // modulus n^2 (nr set)
   const uint32_t* table; // [nwin][2^w][L]

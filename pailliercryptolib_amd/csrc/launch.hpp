@@ -311,6 +311,19 @@ inline bool launch_matvec(int G, int K, const MatvecArgs& a, unsigned blocks, hi
          launch_matvec_part40(G, K, false, a, blocks, s);
 }
 
+// The encrypted segmented sum (hensel_segsum.hpp; k_hensel.hip parts 41-44): one product chain per chunk descriptor, in
+// the geometries matvec_has lists, and -- part 44 -- with the 72 limbs of a 2048-bit key's half on 8 lanes instead of 4
+// (the same pair rows, half the time per product, half the chains per wavefront): levels that leave SIMDs empty either way
+inline bool segsum_wide_has(int G, int K) { return G == 8 && K == 9; }
+bool launch_segsum_part41(int G, int K, const SegsumArgs& a, unsigned blocks, hipStream_t s);
+bool launch_segsum_part42(int G, int K, const SegsumArgs& a, unsigned blocks, hipStream_t s);
+bool launch_segsum_part43(int G, int K, const SegsumArgs& a, unsigned blocks, hipStream_t s);
+bool launch_segsum_part44(int G, int K, const SegsumArgs& a, unsigned blocks, hipStream_t s);
+inline bool launch_segsum(int G, int K, const SegsumArgs& a, unsigned blocks, hipStream_t s) {
+  return launch_segsum_part41(G, K, a, blocks, s) || launch_segsum_part42(G, K, a, blocks, s) ||
+         launch_segsum_part43(G, K, a, blocks, s) || launch_segsum_part44(G, K, a, blocks, s);
+}
+
 // DJN encrypt to pair rows in the same form (k_hensel.hip parts 20, 21, 28): (4,18) 2048-bit keys, (8,14) 3072, (2,19) 1024
 inline bool hensel_fb_encrypt_seq_has(int G, int K) { return (G == 4 && K == 18) || (G == 8 && K == 14) || (G == 2 && K == 19); }
 bool launch_hensel_fb_encrypt_seq_part28(int G, int K, const HenselFbArgs& a, unsigned blocks, hipStream_t s);

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
+#include <utility>
 
 #include "launch.hpp"
 
@@ -224,6 +225,87 @@ int matvec_window(size_t rows, size_t cols, int e_bits, size_t slices, size_t ro
     if (cost < best_cost) { best_cost = cost; best = w; }
   }
   return best;
+}
+
+
+// ---- encrypted segmented sum ----
+bool segsum_sort(const uint32_t* ids, size_t groups, size_t cols, size_t n_segments, std::vector<uint32_t>* perm,
+                 std::vector<size_t>* offsets) {
+  const size_t segments = groups * n_segments;
+  std::vector<size_t> off(segments + 1, 0);
+  for (size_t g = 0; g < groups; ++g)
+    for (size_t j = 0; j < cols; ++j) {
+      const uint32_t id = ids[g * cols + j];
+      if (id == kSegsumNone) continue;
+      if (id >= n_segments) return false;
+      ++off[g * n_segments + id + 1];
+    }
+  for (size_t s = 0; s < segments; ++s) off[s + 1] += off[s];
+  std::vector<uint32_t> p(off[segments]);
+  std::vector<size_t> next(off.begin(), off.end() - 1);
+  for (size_t g = 0; g < groups; ++g)
+    for (size_t j = 0; j < cols; ++j) {   // rising j: equal ids keep their order
+      const uint32_t id = ids[g * cols + j];
+      if (id != kSegsumNone) p[next[g * n_segments + id]++] = (uint32_t)j;
+    }
+  perm->swap(p);
+  offsets->swap(off);
+  return true;
+}
+int segsum_chunk(int G, size_t elements) {
+  const long forced = env_now("PGPU_SEGSUM_CHUNK");
+  if (forced >= 2) return (int)std::min(forced, (long)kSegsumForcedMax);
+  const size_t chains = kSegsumWavesPerSimd * kSimds * (64 / (size_t)G);   // chains that fill the chip
+  return (int)std::max(kSegsumMinChunk, std::min(kSegsumMaxChunk, elements / chains));
+}
+bool segsum_wide_pays(int wide_G, size_t chains) {
+  const size_t ipw = 64 / (size_t)wide_G;
+  return (chains + ipw - 1) / ipw <= kSimds;
+}
+int segsum_levels(int chunk, size_t longest) {
+  int levels = 1;
+  for (size_t m = longest; m > (size_t)chunk; m = (m + (size_t)chunk - 1) / (size_t)chunk) ++levels;
+  return levels;
+}
+void segsum_plan(const std::vector<size_t>& offsets, int chunk, SegsumPlan* plan) {
+  const size_t segments = offsets.empty() ? 0 : offsets.size() - 1, c = (size_t)chunk;
+  plan->chunk = chunk;
+  plan->longest = 0;
+  plan->levels.clear();
+  // the lists still to be multiplied: at level 0 the ranges of perm, afterwards ranges of the partial rows just written
+  struct List { size_t seg, begin, len; };
+  std::vector<List> todo;
+  for (size_t s = 0; s < segments; ++s) {
+    todo.push_back({s, offsets[s], offsets[s + 1] - offsets[s]});
+    plan->longest = std::max(plan->longest, offsets[s + 1] - offsets[s]);
+  }
+  while (!todo.empty()) {
+    SegsumLevel lv;
+    std::vector<List> next;
+    for (const List& l : todo) {
+      if (l.len <= c) {
+        lv.chunks.push_back({(uint64_t)l.begin, (uint32_t)l.len, (uint32_t)l.seg});
+        continue;
+      }
+      const size_t parts = (l.len + c - 1) / c;
+      next.push_back({l.seg, lv.partial_rows, parts});
+      for (size_t k = 0; k < parts; ++k)
+        lv.chunks.push_back({(uint64_t)(l.begin + k * c), (uint32_t)std::min(c, l.len - k * c),
+                             kSegsumPartial | (uint32_t)(lv.partial_rows + k)});
+      lv.partial_rows += parts;
+    }
+    // by len descending, equal lengths in the order made above: a counting sort (len <= chunk <= kSegsumForcedMax)
+    {
+      std::vector<size_t> at(c + 2, 0);
+      for (const SegsumChunk& k : lv.chunks) ++at[c - k.len + 1];
+      for (size_t i = 0; i <= c; ++i) at[i + 1] += at[i];
+      std::vector<SegsumChunk> sorted(lv.chunks.size());
+      for (const SegsumChunk& k : lv.chunks) sorted[at[c - k.len]++] = k;
+      lv.chunks.swap(sorted);
+    }
+    plan->levels.push_back(std::move(lv));
+    todo.swap(next);
+  }
 }
 
 }  // namespace policy

@@ -14,6 +14,11 @@
 #define PAILLIERCRYPTOLIB_AMD_CSRC_POLICY_HPP_
 
 #include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "kargs.hpp"
 
 namespace pgpu {
 namespace policy {
@@ -97,6 +102,54 @@ constexpr size_t kMatvecTableCap = (size_t)256 << 20;
 int matvec_window(size_t rows, size_t cols, int e_bits, size_t slices, size_t row_bytes);
 // products of the schedule above (w, S as given)
 double matvec_products(size_t rows, size_t cols, int e_bits, int w, size_t slices);
+
+
+// ---- the encrypted segmented sum (hensel_segsum.hpp; pgpu_batch_ct_segment_sum, pgpu_ct_segment_sum_plan) ----
+// out[g][s] = prod_{j : ids[g][j] == s} X[j].  A segment of m elements costs m - 1 pair products however it is cut, so the
+// cut decides only how the products spread over the chip and what each chain pays beside them.
+// 1. segsum_sort: a stable counting sort of every group's element numbers by id.  perm holds, group after group and
+//    segment after segment, the element numbers j in rising order; offsets[g * n_segments + s] .. [.. + 1] is the range of
+//    segment s of group g.  Ids equal to kSegsumNone are left out.  false: an id >= n_segments (nothing is written then).
+constexpr uint32_t kSegsumNone = 0xFFFFFFFFu;
+bool segsum_sort(const uint32_t* ids, size_t groups, size_t cols, size_t n_segments, std::vector<uint32_t>* perm,
+                 std::vector<size_t>* offsets);
+// 2. the chunk: one chunk is one product chain of one group of G lanes.  The chunk that gives every SIMD
+//    kSegsumWavesPerSimd wavefronts -- of 64/G chains each -- to work through at level 0,
+//    elements / (kSegsumWavesPerSimd * kSimds * 64/G), but
+//    * at least kSegsumMinChunk: a chunk of c entries leaves one partial row (written once, read once by the next level)
+//      per c - 1 products, one descriptor for the host to make and upload, and every level is a launch of its own;
+//    * at most kSegsumMaxChunk: a chunk is serial, and the wavefronts of a level that are still running when the others
+//      are done leave the chip idle for up to one chunk's time.
+//    The kernels are fastest with MANY short chains -- two resident wavefronts per SIMD cover each other's row loads, and
+//    the queue behind them evens out the tail -- while the host's share of a call grows with the number of chunks; the
+//    sweep behind the three constants is in DESIGN.md section 12 and profiles/segsum_bench.txt.
+//    PGPU_SEGSUM_CHUNK=c, 2 <= c <= kSegsumForcedMax, forces it (larger values are clamped; read at every call: the
+//    tests reach every path with it).
+constexpr size_t kSegsumWavesPerSimd = 8;
+constexpr size_t kSegsumMinChunk = 8;
+constexpr size_t kSegsumMaxChunk = 256;
+constexpr size_t kSegsumForcedMax = 65536;
+int segsum_chunk(int G, size_t elements);
+//    A level whose chains leave SIMDs empty even at 64/wide_G chains per wavefront runs in the form with the same limbs
+//    per half on wide_G > G lanes (2048-bit keys: (8,9) beside (4,18); launch.hpp: segsum_wide_has): the same rows, half
+//    the serial time per product -- small inputs and the last fold levels cost by their depth, not their size.
+bool segsum_wide_pays(int wide_G, size_t chains);
+// 3. levels: a segment of more than `chunk` entries leaves ceil(m / chunk) partial rows, which the next level treats as a
+//    segment of that length: ceil(log_chunk(longest)) levels, at least 1.
+int segsum_levels(int chunk, size_t longest);
+// 4. the plan: per level the chunk descriptors, ordered by len descending (stable), and the number of partial rows the
+//    level writes.  Level 0 walks perm (begin: an entry of perm), the later ones the partial rows of the level before
+//    (begin: a row).  dst: the segment number g * n_segments + s for the last chunk of a segment, else kSegsumPartial | row.
+struct SegsumLevel {
+  std::vector<SegsumChunk> chunks;
+  size_t partial_rows = 0;
+};
+struct SegsumPlan {
+  int chunk = 0;
+  size_t longest = 0;
+  std::vector<SegsumLevel> levels;    // size() == segsum_levels(chunk, longest)
+};
+void segsum_plan(const std::vector<size_t>& offsets, int chunk, SegsumPlan* plan);
 
 }  // namespace policy
 }  // namespace pgpu

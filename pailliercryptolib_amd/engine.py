@@ -179,6 +179,35 @@ class PublicKey:
                     L.pgpu_batch_destroy(h)
         return limbs_to_ints(out)
 
+    def segment_sum(self, x, ids, n_segments):
+        """Encrypted segmented sum: x a list of ciphertexts (ints modulo n^2), ids one flat list of segment numbers (one
+        group) or a list of such lists (several groupings of the same x); None leaves an element out of that group ->
+        for one group the list of n_segments ciphertexts prod_{j: ids[j] == s} x[j] mod n^2, i.e. encryptions of the
+        per-segment sums mod n, for several groups all of them, group after group (an empty segment: 1).  One
+        pgpu_batch_ct_segment_sum call on resident batches; there is no element-wise fall-back."""
+        groups = [list(r) for r in ids] if len(ids) and isinstance(ids[0], (list, tuple)) else [list(ids)]
+        cols, n_segments = len(x), int(n_segments)
+        if cols == 0 or n_segments <= 0 or any(len(r) != cols for r in groups):
+            raise RuntimeError("segment sum error: Size mismatch!")
+        flat = np.array([_capi.SEGMENT_NONE if v is None else int(v) for r in groups for v in r], dtype=np.int64)
+        if flat.min() < 0 or ((flat >= n_segments) & (flat != _capi.SEGMENT_NONE)).any():
+            raise RuntimeError("segment sum error: a segment id is not below n_segments")
+        flat = flat.astype(np.uint32)
+        L = _capi.lib()
+        W = 2 * self.n_words
+        hx, ho = ctypes.c_void_p(), ctypes.c_void_p()
+        try:
+            xa = ints_to_limbs([int(v) for v in x], W)
+            _capi.check(L.pgpu_batch_upload(_ptr(xa), cols, W, W, ctypes.byref(hx)))
+            _capi.check(L.pgpu_batch_ct_segment_sum(self._h, hx, _ptr(flat), len(groups), n_segments, ctypes.byref(ho)))
+            out = np.empty((len(groups) * n_segments, W), dtype=np.uint64)
+            _capi.check(L.pgpu_batch_download(ho, _ptr(out)))
+        finally:
+            for h in (hx, ho):
+                if h:
+                    L.pgpu_batch_destroy(h)
+        return limbs_to_ints(out)
+
 
 class PrivateKey:
     """Host-side mirror of ipcl::PrivateKey::decrypt (CRT path, pri_key.cpp:65-90,114-157)."""
