@@ -16,6 +16,7 @@ namespace ext {   // include/ipcl/ext/linear.hpp
 CipherText matVec(const PlainText& w, std::size_t rows, const CipherText& x);
 // include/ipcl/ext/aggregate.hpp
 CipherText segmentSum(const CipherText& x, const std::vector<uint32_t>& ids, std::size_t n_segments, std::size_t groups);
+CipherText segmentScan(const CipherText& x, std::size_t seg_len, bool reverse);
 }
 
 class CipherText : public BaseText {
@@ -48,6 +49,9 @@ class CipherText : public BaseText {
                                     std::size_t groups);
   // prod_{j: ids[g][j] == s} this[j]: csrc/host/aggregate.cpp
   CipherText segmentMap(const std::vector<uint32_t>& ids, std::size_t n_segments, std::size_t groups) const;
+  friend CipherText ext::segmentScan(const CipherText& x, std::size_t seg_len, bool reverse);
+  // prod_{u <= t} this[r][u] (reverse: u >= t), this read as [m_size / seg_len][seg_len]: csrc/host/aggregate.cpp
+  CipherText segmentScanMap(std::size_t seg_len, bool reverse) const;
   CipherText(const PublicKey& pk, std::shared_ptr<detail::DeviceBatch> dev);
   CipherText(std::shared_ptr<PublicKey> pk, std::shared_ptr<detail::DeviceBatch> dev);
   std::shared_ptr<PublicKey> m_pk;

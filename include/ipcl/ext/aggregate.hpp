@@ -6,6 +6,12 @@
 //       Y[g][s] = prod_{j : ids[g][j] == s} X[j] mod n^2 -- a histogram of encrypted gradients per feature bin, a per-key
 //       aggregate, a per-client sum, the pooling step after an encrypted layer
 //
+//   segmentScan(x, seg_len, reverse = false)
+//       x read as [x.getSize() / seg_len][seg_len]; y[r][t] = sum of x[r][u], u <= t (reverse: u >= t) under the encryption:
+//       Y[r][t] = prod_{u <= t} X[r][u] mod n^2 -- the cumulative sum over the bins of every histogram that segmentSum made
+//       (seg_len = n_segments), both sides of every split without a subtraction; a running total over one long vector
+//       with seg_len = x.getSize().  The scan is inclusive.  seg_len must be positive and divide x.getSize().
+//
 // ids: groups*cols plaintext segment numbers, row-major, each below n_segments or kSegmentNone (the element is left out
 // of that group: a missing value, a sample outside the node).  groups > 1 reads the same x once per group under another
 // grouping.  An empty segment yields the ciphertext 1 (it decrypts to 0).  One fused launch sequence on the GPU
@@ -30,6 +36,7 @@ constexpr uint32_t kSegmentNone = 0xFFFFFFFFu;
 
 CipherText segmentSum(const CipherText& x, const std::vector<uint32_t>& ids, std::size_t n_segments,
                       std::size_t groups = 1);
+CipherText segmentScan(const CipherText& x, std::size_t seg_len, bool reverse = false);
 
 }  // namespace ext
 }  // namespace ipcl

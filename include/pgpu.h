@@ -347,6 +347,32 @@ int pgpu_batch_ct_segment_sum(const pgpu_pubkey* key, const pgpu_batch* x, const
  * policy.hpp: segsum_*; PGPU_SEGSUM_CHUNK=c (c >= 2) forces the chunk.
  * PGPU_ERR_UNSUPPORTED: no pair rows for keys of key_bits. */
 int pgpu_ct_segment_sum_plan(int key_bits, size_t elements, size_t segments, size_t longest_segment, int* chunk, int* levels);
+/* Encrypted segmented prefix sum (the cumulative sum over the bins of every histogram, a running total, a CDF over
+ * encrypted values): x a resident ciphertext batch of count = rows * seg_len elements (pair rows, or uploaded plain
+ * ciphertext words: converted on the way in), read as [rows][seg_len]; the scan is inclusive:
+ *     out[r][t] = prod_{ u <= t } x[r][u] mod n^2     i.e. Dec(out[r][t]) = sum_{u <= t} Dec(x[r][u]) mod n
+ * and with PGPU_SCAN_REVERSE in flags the product runs over u >= t (suffix sums: the right-hand side of every split).
+ * The result is an ordinary resident ciphertext batch of count elements in pair rows on the lane of x -- the layout
+ * [groups][n_segments] of a pgpu_batch_ct_segment_sum result is scanned with seg_len = n_segments.  A row of at most
+ * `chunk` entries is one product chain (seg_len - 1 products, one launch); a longer row is cut into chunks: the chunk
+ * totals are multiplied up, scanned by the same procedure, and every chunk is walked again from the scanned total before
+ * it ("Encrypted segmented prefix sum"), about 2 * count products.
+ * PGPU_ERR_INVALID_PARAM: null / stale handles, seg_len == 0, count(x) % seg_len != 0, a flag bit other than
+ * PGPU_SCAN_REVERSE, ciphertext width mismatch, a batch of another key, more chunks than a 32-bit carry index addresses.
+ * PGPU_ERR_UNSUPPORTED: keys without pair rows (beyond 3072 bits; PGPU_PAIR_ROWS=0 / PGPU_HENSEL=0), pools of more than one
+ * GPU, and the masked table-gather policy.  SIDE CHANNELS: the address stream of this call depends only on rows, seg_len
+ * and the plan -- no index list, nothing derived from a value; the refusal under pgpu_set_table_gather_policy(1) is kept
+ * for symmetry with pgpu_batch_ct_matvec and pgpu_batch_ct_segment_sum, so that one rule covers the aggregation calls.
+ * All refusals are decided on the host before any launch and leave *out untouched. */
+#define PGPU_SCAN_REVERSE 1u
+int pgpu_batch_ct_segment_scan(const pgpu_pubkey* key, const pgpu_batch* x, size_t seg_len, unsigned flags, pgpu_batch** out);
+/* What a call of this shape would run (host-side query, needs no device).  chunk: the entries one product chain walks
+ * (seg_len itself when one chain per row is the plan); levels: the depth of the hierarchy, 1 when seg_len <= chunk -- a
+ * call runs 2 * levels - 1 launches; products: the pair products of all launches, padding excluded.  The rule is
+ * policy.hpp: segscan_*; PGPU_SEGSCAN_CHUNK=c (c >= 2) forces the chunk, read at every call.
+ * PGPU_ERR_UNSUPPORTED: no pair rows for keys of key_bits.  PGPU_ERR_INVALID_PARAM: rows == 0, seg_len == 0, more chunks
+ * than a 32-bit carry index addresses. */
+int pgpu_ct_segment_scan_plan(int key_bits, size_t rows, size_t seg_len, int* chunk, int* levels, size_t* products);
 
 /* ---- instrumentation used by bench.py (roofline) ----
  * With timing enabled every kernel launch is bracketed by two HIP events recorded on the stream
@@ -359,7 +385,8 @@ typedef enum pgpu_kernel_kind {
   PGPU_KERNEL_CRT = 3,        /* crt_kernel (decrypt stage 2) */
   PGPU_KERNEL_FB_ENCRYPT = 4, /* fb_encrypt_kernel (DJN encrypt, fixed-base) */
   PGPU_KERNEL_MATVEC = 5,     /* every launch of pgpu_batch_ct_matvec: table build, multi-exponentiation, fold */
-  PGPU_KERNEL_SEGSUM = 6      /* every launch of pgpu_batch_ct_segment_sum: one per level */
+  PGPU_KERNEL_SEGSUM = 6,     /* every launch of pgpu_batch_ct_segment_sum: one per level */
+  PGPU_KERNEL_SEGSCAN = 7     /* every launch of pgpu_batch_ct_segment_scan: up-sweeps (segsum_kernel) and scans */
 } pgpu_kernel_kind;
 int pgpu_set_timing(int enabled);
 int pgpu_timing_collect(int* kinds, double* ms, int max_entries);

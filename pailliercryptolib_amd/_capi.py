@@ -37,9 +37,11 @@ SYMBOLS = [
     "pgpu_timing_collect_trace",
     "pgpu_batch_ct_matvec", "pgpu_ct_matvec_plan",
     "pgpu_batch_ct_segment_sum", "pgpu_ct_segment_sum_plan",
+    "pgpu_batch_ct_segment_scan", "pgpu_ct_segment_scan_plan",
 ]
 FEATURE_4096_SPLIT = 1
 SEGMENT_NONE = 0xFFFFFFFF      # PGPU_SEGMENT_NONE: the element is left out of that group
+SCAN_REVERSE = 1               # PGPU_SCAN_REVERSE: suffix instead of prefix products
 
 _lib = None
 
@@ -175,6 +177,10 @@ def lib():
     L.pgpu_batch_ct_segment_sum.restype = c_int
     L.pgpu_ct_segment_sum_plan.argtypes = [c_int, c_size_t, c_size_t, c_size_t, POINTER(c_int), POINTER(c_int)]
     L.pgpu_ct_segment_sum_plan.restype = c_int
+    L.pgpu_batch_ct_segment_scan.argtypes = [c_void_p, c_void_p, c_size_t, ctypes.c_uint, POINTER(c_void_p)]
+    L.pgpu_batch_ct_segment_scan.restype = c_int
+    L.pgpu_ct_segment_scan_plan.argtypes = [c_int, c_size_t, c_size_t, POINTER(c_int), POINTER(c_int), POINTER(c_size_t)]
+    L.pgpu_ct_segment_scan_plan.restype = c_int
     _lib = L
     return L
 

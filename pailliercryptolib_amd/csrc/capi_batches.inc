@@ -805,6 +805,150 @@ int pgpu_batch_ct_segment_sum(const pgpu_pubkey* key, const pgpu_batch* x, const
   return PGPU_OK;
 }
 
+// ---- encrypted segmented prefix sum (hensel_segscan.hpp; policy.hpp: segscan_*) ----
+int pgpu_ct_segment_scan_plan(int key_bits, size_t rows, size_t seg_len, int* chunk, int* levels, size_t* products) {
+  if (key_bits < 1 || rows == 0 || seg_len == 0)
+    return fail(PGPU_ERR_INVALID_PARAM, "segment scan plan: key_bits, rows and seg_len must be positive");
+  int G = 0, K = 0;
+  if (!policy::matvec_geometry(key_bits, &G, &K))
+    return fail(PGPU_ERR_UNSUPPORTED, "segment scan: keys of this size have no pair rows (1024- to 3072-bit key classes only)");
+  const int c = policy::segscan_chunk(G, rows, seg_len);
+  if (!policy::segscan_fits(c, rows, seg_len))
+    return fail(PGPU_ERR_INVALID_PARAM, "segment scan plan: more chunks than a 32-bit carry index addresses");
+  if (chunk) *chunk = c;
+  if (levels) *levels = policy::segscan_levels(c, seg_len);
+  if (products) *products = policy::segscan_products(c, rows, seg_len);
+  return PGPU_OK;
+}
+
+int pgpu_batch_ct_segment_scan(const pgpu_pubkey* key, const pgpu_batch* x, size_t seg_len, unsigned flags, pgpu_batch** out) {
+  RC_TRY(rt::check_ready());
+  if (!key || !x || !out) return fail(PGPU_ERR_INVALID_PARAM, "null argument");
+  RC_TRY(check_gen(key->gen, "key"));
+  RC_TRY(check_gen(x->gen, "batch"));
+  const int W = 2 * key->n_words;
+  const size_t count = x->count;
+  if (seg_len == 0 || count == 0 || count % seg_len != 0)
+    return fail(PGPU_ERR_INVALID_PARAM, "segment scan error: seg_len must be positive and divide count(x)");
+  if (flags & ~PGPU_SCAN_REVERSE) return fail(PGPU_ERR_INVALID_PARAM, "segment scan error: unknown flag bit (PGPU_SCAN_REVERSE is the only one)");
+  if (x->words != W) return fail(PGPU_ERR_INVALID_PARAM, "segment scan error: ciphertext width mismatch");
+  if (!same_domain(x->mont, key->nsq)) return fail(PGPU_ERR_INVALID_PARAM, "segment scan error: batch belongs to a different key");
+  if (rt::pool_size() > 1)
+    return fail(PGPU_ERR_UNSUPPORTED, "segment scan: pools of more than one GPU are not supported (rows are not sharded yet)");
+  const pgpu_pubkey::PubForm* pf = pair_form(key);
+  if (!pf || !pgpu::matvec_has(pf->H, pf->K))
+    return fail(PGPU_ERR_UNSUPPORTED, "segment scan: key has no pair form (1024- to 3072-bit keys; PGPU_PAIR_ROWS=0 / PGPU_HENSEL=0 switch it off)");
+  // the address stream here depends on rows, seg_len and the plan alone; the call is refused under the masked policy all
+  // the same, like its two siblings: one rule for the aggregation calls
+  if (g_ct_gather.load())
+    return fail(PGPU_ERR_UNSUPPORTED, "segment scan: the masked table-gather policy is on (pgpu_set_table_gather_policy / PGPU_CT_GATHER); "
+                                      "the aggregation calls on resident ciphertexts have no masked variant");
+  if (x->pair_l2 && (x->pair_l2 != pf->H * pf->K || !(x->pair_form->n == key->n)))
+    return fail(PGPU_ERR_INVALID_PARAM, "segment scan error: batch belongs to a different key");
+  // the plan, on the host
+  const int G = pf->H, K = pf->K, l2 = G * K;
+  const size_t LQ = (size_t)2 * l2, row_bytes = LQ * sizeof(uint32_t), rows = count / seg_len;
+  const int chunk = policy::segscan_chunk(G, rows, seg_len);
+  if (!policy::segscan_fits(chunk, rows, seg_len))
+    return fail(PGPU_ERR_INVALID_PARAM, "segment scan error: more chunks than a 32-bit carry index addresses (a larger PGPU_SEGSCAN_CHUNK, or fewer rows per call)");
+  policy::SegscanPlan plan;
+  policy::segscan_plan(rows, seg_len, chunk, (flags & PGPU_SCAN_REVERSE) != 0, &plan);
+  static_assert(sizeof(pgpu::SegsumChunk) == 16 && sizeof(pgpu::SegscanChunk) == 16, "descriptors are packed into one image");
+  // one image for the device: per level the up-sweep descriptors, then the scan descriptors.  Scratch rows: per level but
+  // the deepest its totals and, beside them, the carries the level below makes of them
+  const size_t nl = plan.levels.size();
+  size_t image_bytes = 0, scratch_rows = 0;
+  std::vector<size_t> up_at(nl), scan_at(nl), totals_at(nl), carry_at(nl);
+  for (size_t l = 0; l < nl; ++l) {
+    const auto& lv = plan.levels[l];
+    up_at[l] = image_bytes;
+    image_bytes += lv.up.size() * sizeof(pgpu::SegsumChunk);
+    scan_at[l] = image_bytes;
+    image_bytes += lv.scan.size() * sizeof(pgpu::SegscanChunk);
+    totals_at[l] = scratch_rows;
+    carry_at[l] = scratch_rows + lv.totals;
+    scratch_rows += 2 * lv.totals;
+  }
+  std::vector<char> image(image_bytes, 0);
+  for (size_t l = 0; l < nl; ++l) {
+    const auto& lv = plan.levels[l];
+    if (!lv.up.empty()) std::memcpy(image.data() + up_at[l], lv.up.data(), lv.up.size() * sizeof(pgpu::SegsumChunk));
+    std::memcpy(image.data() + scan_at[l], lv.scan.data(), lv.scan.size() * sizeof(pgpu::SegscanChunk));
+  }
+  std::unique_ptr<pgpu_batch> tx;
+  RC_TRY(as_pair_batch(key, x, &x, &tx));
+  std::unique_ptr<pgpu_batch> o;
+  RC_TRY(new_batch(count, W, &o, l2, x->lane));
+  o->pair_form = pair_form_shared(key);
+  rt::Device& dev = rt::device(0);
+  rt::DeviceGuard g(dev.ordinal);
+  hipStream_t s = dev.bs(x->lane);
+  // plan image, totals and carries: the block arena, on the lane's stream like the operands themselves -- what the arena
+  // hands out again it hands to this stream, behind the kernels below
+  rt::DevMem dimage, scratch;
+  RC_TRY(dimage.alloc(dev, s, image_bytes));
+  if (scratch_rows) RC_TRY(scratch.alloc(dev, s, scratch_rows * row_bytes));
+  if (image_bytes <= kBounceBytes) {
+    Bounce& bn = bounce();
+    RC_TRY(bn.ready());
+    std::memcpy(bn.p, image.data(), image_bytes);
+    HIP_TRY(hipMemcpyAsync(dimage.p, bn.p, image_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(bn.ev, s));
+    bn.pending = true;
+  } else {   // through a worker lane's staging buffers, queued on the same stream: nothing is waited for
+    rt::TaskGroup tg;
+    void* dst = dimage.p;
+    const char* src = image.data();
+    tg.run(dev, [=](rt::Lane& lane) -> int { return lane.h2d(dst, src, image_bytes, s); });
+    RC_TRY(tg.wait());
+  }
+  // the form with the same limbs per half on more lanes, for the up-sweeps that leave SIMDs empty (segsum_kernel only)
+  const pgpu_pubkey::PubForm* wide = nullptr;
+  for (const auto& alt : key->hforms)
+    if (alt->H * alt->K == l2 && alt->H > G && pgpu::segsum_wide_has(alt->H, alt->K)) wide = alt.get();
+  uint32_t* const sc = (uint32_t*)scratch.p;
+  // level l reads in(l) and writes res(l): x and the result batch, or the totals and the carries of the level above
+  auto in = [&](size_t l) -> const uint32_t* { return l == 0 ? x->prow(0) : sc + totals_at[l - 1] * LQ; };
+  auto res = [&](size_t l) -> uint32_t* { return l == 0 ? o->prow(0) : sc + carry_at[l - 1] * LQ; };
+  for (size_t l = 0; l + 1 < nl; ++l) {   // up-sweep: the chunk totals, level by level
+    const auto& lv = plan.levels[l];
+    const pgpu_pubkey::PubForm* lf = wide && policy::segsum_wide_pays(wide->H, lv.up.size()) ? wide : pf;
+    pgpu::SegsumArgs a{};
+    a.ctx = hensel_pub_view(lf, dev.index);
+    a.src = in(l);
+    a.perm = nullptr;
+    a.chunks = (const pgpu::SegsumChunk*)((const char*)dimage.p + up_at[l]);
+    a.n_chunks = lv.up.size();
+    a.out = nullptr;                       // (every descriptor names a row of partial)
+    a.partial = sc + totals_at[l] * LQ;
+    const size_t ipw = 64 / (size_t)lf->H, waves = (a.n_chunks + ipw - 1) / ipw;
+    TimerScope t(dev, s, PGPU_KERNEL_SEGSCAN, PGPU_FORM_SEQ);
+    if (!pgpu::launch_segsum(lf->H, lf->K, a, (unsigned)((waves + pgpu::kWavesPerWG - 1) / pgpu::kWavesPerWG), s))
+      return fail(PGPU_ERR_UNSUPPORTED, "segment sum kernels not compiled for this key class");
+    HIP_TRY(hipGetLastError());
+    t.stop();
+  }
+  for (size_t l = nl; l-- > 0;) {         // down-sweep: the deepest level has no carries, every other one those below it
+    const auto& lv = plan.levels[l];
+    pgpu::SegscanArgs a{};
+    a.ctx = hensel_pub_view(pf, dev.index);
+    a.src = in(l);
+    a.carry = l + 1 < nl ? res(l + 1) : nullptr;
+    a.chunks = (const pgpu::SegscanChunk*)((const char*)dimage.p + scan_at[l]);
+    a.n_chunks = lv.scan.size();
+    a.out = res(l);
+    a.step = lv.reverse ? -1 : 1;
+    const size_t ipw = 64 / (size_t)G, waves = (a.n_chunks + ipw - 1) / ipw;
+    TimerScope t(dev, s, PGPU_KERNEL_SEGSCAN, PGPU_FORM_SEQ);
+    if (!pgpu::launch_segscan(G, K, a, (unsigned)((waves + pgpu::kWavesPerWG - 1) / pgpu::kWavesPerWG), s))
+      return fail(PGPU_ERR_UNSUPPORTED, "segment scan kernels not compiled for this key class");
+    HIP_TRY(hipGetLastError());
+    t.stop();
+  }
+  *out = o.release();
+  return PGPU_OK;
+}
+
 int pgpu_set_batch_lane(int lane) {
   if (lane < 0 || lane >= rt::kBatchLanes) return fail(PGPU_ERR_INVALID_PARAM, "batch lane out of range (pgpu_batch_lanes())");
   t_batch_lane = lane;

@@ -1,5 +1,5 @@
 // pailliercryptolib_amd -- instantiations of the split-form CRT-decrypt exponentiation (hensel.hpp), split over
-// PGPU_PART = 0..44 so that they compile in parallel (38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
+// PGPU_PART = 0..47 so that they compile in parallel (38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 45-47: the encrypted segmented prefix sum; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
 // the two-wavefronts-per-SIMD build of the (2,19) decrypt form; 11-13: element-wise operations on pair rows).
 #include "hensel_seq.hpp"
 #include "launch.hpp"
@@ -18,9 +18,12 @@
 #if defined(PGPU_PART) && PGPU_PART >= 41 && PGPU_PART <= 44
 #include "hensel_segsum.hpp"    // the encrypted segmented sum: one product chain per chunk of a sorted index list
 #endif
+#if defined(PGPU_PART) && PGPU_PART >= 45 && PGPU_PART <= 47
+#include "hensel_segscan.hpp"   // the encrypted segmented prefix sum: one product chain per chunk, every step stored
+#endif
 
 #ifndef PGPU_PART
-#error "compile with -DPGPU_PART=0..44 (15 and 30 are retired)"
+#error "compile with -DPGPU_PART=0..47 (15 and 30 are retired)"
 #endif
 
 namespace pgpu {
@@ -483,6 +486,26 @@ bool PGPU_MV_NAME(int G, int K, bool table, const MatvecArgs& a, unsigned blocks
 bool PGPU_SS_NAME(int G, int K, const SegsumArgs& a, unsigned blocks, hipStream_t s) {
   if (G != PGPU_SS_G || K != PGPU_SS_K) return false;
   hipLaunchKernelGGL((segsum_kernel<PGPU_SS_G, PGPU_SS_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
+  return true;
+}
+#elif PGPU_PART >= 45 && PGPU_PART <= 47
+// the encrypted segmented prefix sum (hensel_segscan.hpp): one geometry per part
+#if PGPU_PART == 45
+#define PGPU_SC_G 4
+#define PGPU_SC_K 18
+#define PGPU_SC_NAME launch_segscan_part45
+#elif PGPU_PART == 46
+#define PGPU_SC_G 8
+#define PGPU_SC_K 14
+#define PGPU_SC_NAME launch_segscan_part46
+#else
+#define PGPU_SC_G 2
+#define PGPU_SC_K 19
+#define PGPU_SC_NAME launch_segscan_part47
+#endif
+bool PGPU_SC_NAME(int G, int K, const SegscanArgs& a, unsigned blocks, hipStream_t s) {
+  if (G != PGPU_SC_G || K != PGPU_SC_K) return false;
+  hipLaunchKernelGGL((segscan_kernel<PGPU_SC_G, PGPU_SC_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
   return true;
 }
 #else

@@ -333,6 +333,27 @@ struct SegsumArgs {
   uint32_t* partial;         // [..][2*L2] partial rows this level writes
 };
 
+// Encrypted segmented prefix sum on pair rows (hensel_segscan.hpp): one product chain per chunk descriptor, EVERY
+// intermediate value stored.  A chunk walks the rows src[begin], src[begin + step], ..., src[begin + (len - 1) * step]
+// (step = +1 or -1, one value per launch) and writes the running product after entry t to out[begin + t * step].  carry
+// names a row of `carry` that the chain starts from (the scanned total of the chunks before it in scan direction), or
+// kSegscanNoCarry: the chain starts as entry 0 and out[begin] is that row unchanged.
+struct SegscanChunk {
+  uint64_t begin;            // first row of src / out the chain touches (step -1: the highest)
+  uint32_t len;              // >= 1
+  uint32_t carry;
+};
+constexpr uint32_t kSegscanNoCarry = 0xFFFFFFFFu;
+struct SegscanArgs {
+  HenselPubDev ctx;
+  const uint32_t* src;       // [..][2*L2] pair rows: the ciphertexts, or the chunk totals of the level above
+  const uint32_t* carry;     // [..][2*L2] pair rows: the scanned totals (null: no descriptor of the launch names one)
+  const SegscanChunk* chunks;// [n_chunks], ordered by len descending
+  size_t n_chunks;           // >= 1
+  uint32_t* out;             // [..][2*L2] as many rows as src, never the same memory
+  int step;                  // +1: prefix products, -1: suffix products
+};
+
 struct FixedBaseArgs {
   ModCtxDev ctx;         // modulus n^2 (nr set)
   const uint32_t* table; // [nwin][2^w][L]

@@ -324,6 +324,16 @@ inline bool launch_segsum(int G, int K, const SegsumArgs& a, unsigned blocks, hi
          launch_segsum_part43(G, K, a, blocks, s) || launch_segsum_part44(G, K, a, blocks, s);
 }
 
+// The encrypted segmented prefix sum (hensel_segscan.hpp; k_hensel.hip parts 45-47): one product chain per chunk
+// descriptor with every intermediate row stored, in the geometries matvec_has lists (no (8,9) form: DESIGN.md section 13)
+bool launch_segscan_part45(int G, int K, const SegscanArgs& a, unsigned blocks, hipStream_t s);
+bool launch_segscan_part46(int G, int K, const SegscanArgs& a, unsigned blocks, hipStream_t s);
+bool launch_segscan_part47(int G, int K, const SegscanArgs& a, unsigned blocks, hipStream_t s);
+inline bool launch_segscan(int G, int K, const SegscanArgs& a, unsigned blocks, hipStream_t s) {
+  return launch_segscan_part45(G, K, a, blocks, s) || launch_segscan_part46(G, K, a, blocks, s) ||
+         launch_segscan_part47(G, K, a, blocks, s);
+}
+
 // DJN encrypt to pair rows in the same form (k_hensel.hip parts 20, 21, 28): (4,18) 2048-bit keys, (8,14) 3072, (2,19) 1024
 inline bool hensel_fb_encrypt_seq_has(int G, int K) { return (G == 4 && K == 18) || (G == 8 && K == 14) || (G == 2 && K == 19); }
 bool launch_hensel_fb_encrypt_seq_part28(int G, int K, const HenselFbArgs& a, unsigned blocks, hipStream_t s);

@@ -308,5 +308,72 @@ void segsum_plan(const std::vector<size_t>& offsets, int chunk, SegsumPlan* plan
   }
 }
 
+
+// ---- encrypted segmented prefix sum ----
+int segscan_chunk(int G, size_t rows, size_t seg_len) {
+  const long forced = env_now("PGPU_SEGSCAN_CHUNK");
+  if (forced >= 2) return (int)std::min(forced, (long)kSegscanForcedMax);
+  const size_t whole = std::max<size_t>(1, std::min<size_t>(seg_len, (size_t)1 << 30));
+  const size_t chains = kSegscanWavesPerSimd * kSimds * (64 / (size_t)G);   // chains that fill the chip
+  if (rows >= chains || seg_len <= kSegscanMinChunk) return (int)whole;
+  const size_t nchunks = (chains + std::max<size_t>(1, rows) - 1) / std::max<size_t>(1, rows);
+  return (int)std::min(whole, std::max(kSegscanMinChunk, seg_len / nchunks));
+}
+int segscan_levels(int chunk, size_t seg_len) {
+  const size_t c = (size_t)chunk;
+  int levels = 1;
+  for (size_t m = seg_len; m > c; m = (m + c - 1) / c - 1) ++levels;
+  return levels;
+}
+size_t segscan_products(int chunk, size_t rows, size_t seg_len) {
+  const size_t c = (size_t)chunk;
+  size_t products = 0;
+  for (size_t m = seg_len;; m = (m + c - 1) / c - 1) {
+    products += rows * (m ? m - 1 : 0);
+    if (m <= c) return products;
+    products += rows * ((m + c - 1) / c - 1) * (c - 1);
+  }
+}
+bool segscan_fits(int chunk, size_t rows, size_t seg_len) {
+  const size_t c = (size_t)chunk, kMax = (size_t)1 << 31;
+  if (seg_len && rows > ((size_t)1 << 62) / seg_len) return false;
+  if (seg_len <= c) return seg_len < ((size_t)1 << 32);            // (len is a 32-bit field)
+  return rows < kMax && (seg_len + c - 1) / c - 1 < kMax / std::max<size_t>(1, rows);
+}
+void segscan_plan(size_t rows, size_t seg_len, int chunk, bool reverse, SegscanPlan* plan) {
+  const size_t c = (size_t)chunk;
+  plan->chunk = chunk;
+  plan->products = 0;
+  plan->levels.clear();
+  size_t m = seg_len;
+  for (bool rev = reverse;; rev = false) {
+    SegscanLevel lv;
+    lv.rows = rows;
+    lv.seg_len = m;
+    lv.reverse = rev;
+    const size_t nch = m <= c ? 1 : (m + c - 1) / c, head = std::min(c, m);
+    lv.totals = rows * (nch - 1);
+    // chunk k of a row in scan direction covers c entries from entry k * c of the scan; the lowest row of x among them
+    for (size_t r = 0; r < rows; ++r)
+      for (size_t k = 0; k + 1 < nch; ++k)
+        lv.up.push_back({(uint64_t)(rev ? r * m + m - (k + 1) * c : r * m + k * c), (uint32_t)c,
+                         kSegsumPartial | (uint32_t)(r * (nch - 1) + k)});
+    plan->products += lv.totals * (c - 1);
+    // by len descending: the whole chunks, then the last chunk of every row where it is shorter
+    for (int pass = 0; pass < 2; ++pass)
+      for (size_t r = 0; r < rows; ++r)
+        for (size_t k = 0; k < nch; ++k) {
+          const size_t len = std::min(c, m - k * c);
+          if ((len == head) != (pass == 0)) continue;
+          lv.scan.push_back({(uint64_t)(rev ? r * m + m - 1 - k * c : r * m + k * c), (uint32_t)len,
+                             k ? (uint32_t)(r * (nch - 1) + k - 1) : kSegscanNoCarry});
+        }
+    plan->products += rows * (m - 1);
+    plan->levels.push_back(std::move(lv));
+    if (nch == 1) return;
+    m = nch - 1;
+  }
+}
+
 }  // namespace policy
 }  // namespace pgpu

@@ -151,6 +151,56 @@ struct SegsumPlan {
 };
 void segsum_plan(const std::vector<size_t>& offsets, int chunk, SegsumPlan* plan);
 
+
+// ---- the encrypted segmented prefix sum (hensel_segscan.hpp; pgpu_batch_ct_segment_scan, pgpu_ct_segment_scan_plan) ----
+// out[r][t] = prod_{u <= t} X[r][u] (reverse: u >= t), x read as [rows][seg_len].  One chain of one group of G lanes
+// scans a row of m entries with m - 1 products, which is all the work there is; a row longer than the chunk is scanned by
+// reduce-then-scan and costs about twice that:
+//   up-sweep    the chunks of a row are counted in scan direction (reverse: from the row's end), each of `chunk` entries
+//               but the last.  segsum_kernel (perm == null) multiplies every chunk but the last into a total: rows *
+//               (nchunks - 1) SegsumChunks of len chunk, total k of row r at row r * (nchunks - 1) + k of the level's
+//               totals;
+//   recursion   the totals, [rows][nchunks - 1], are scanned FORWARD by the same procedure (they are already numbered in
+//               scan direction): the carries;
+//   down-sweep  segscan_kernel walks every chunk: chunk 0 of a row starts as its first entry, chunk k > 0 from carry
+//               k - 1 of its row, and every running product is stored.
+// 1. the chunk: seg_len itself -- one level, one launch, no product more than needed -- when the rows alone give every
+//    SIMD kSegscanWavesPerSimd wavefronts of 64/G chains (the fill segsum_chunk aims at), or when seg_len is at most
+//    kSegscanMinChunk; otherwise the chunk that makes rows * nchunks reach that fill, at least kSegscanMinChunk (a chunk of
+//    c entries leaves a total and a carry row, two descriptors, and every level is two launches).  The figures are
+//    segsum_chunk's; the sweep that is to confirm them (tools/bench_segscan.py --sweep) is described in DESIGN.md
+//    section 13.  PGPU_SEGSCAN_CHUNK=c, 2 <= c <= kSegscanForcedMax, forces
+//    it (larger values are clamped; read at every call).
+constexpr size_t kSegscanWavesPerSimd = 8;
+constexpr size_t kSegscanMinChunk = 8;
+constexpr size_t kSegscanForcedMax = 65536;
+int segscan_chunk(int G, size_t rows, size_t seg_len);
+// 2. levels: the depth of the hierarchy, 1 for seg_len <= chunk; a call runs 2 * levels - 1 launches (an up-sweep per
+//    level but the deepest, then a scan per level).  products: the pair products of all of them, padding excluded:
+//    rows * (seg_len - 1) for one level, else rows * ((seg_len - 1) + (nchunks - 1) * (chunk - 1)) plus the recursion's.
+int segscan_levels(int chunk, size_t seg_len);
+size_t segscan_products(int chunk, size_t rows, size_t seg_len);
+//    false: the totals of level 0 -- the most any level has -- are more rows than a descriptor's 31-bit total / 32-bit carry
+//    field names, or rows * seg_len overflows
+bool segscan_fits(int chunk, size_t rows, size_t seg_len);
+// 3. the plan: levels[0] reads x and writes the result; levels[l] reads the totals of level l - 1 and writes its carries.
+//    Execution order: up of level 0, 1, ..., then scan of the deepest level, ..., 1, 0.  scan is ordered by len descending
+//    (only the last chunk of a row is shorter).  begin: the first row of the level's input the chain touches (reverse: the
+//    highest); carry: a row of what level l + 1 wrote, or kSegscanNoCarry.
+struct SegscanLevel {
+  size_t rows = 0, seg_len = 0;       // the level's input (and output) as [rows][seg_len]
+  bool reverse = false;
+  std::vector<SegsumChunk> up;        // empty in the deepest level
+  size_t totals = 0;                  // rows the up-sweep writes = rows * seg_len of the next level
+  std::vector<SegscanChunk> scan;
+};
+struct SegscanPlan {
+  int chunk = 0;
+  size_t products = 0;                // == segscan_products(chunk, rows, seg_len)
+  std::vector<SegscanLevel> levels;   // size() == segscan_levels(chunk, seg_len)
+};
+void segscan_plan(size_t rows, size_t seg_len, int chunk, bool reverse, SegscanPlan* plan);
+
 }  // namespace policy
 }  // namespace pgpu
 

@@ -208,6 +208,29 @@ class PublicKey:
                     L.pgpu_batch_destroy(h)
         return limbs_to_ints(out)
 
+    def segment_scan(self, x, seg_len, reverse=False):
+        """Encrypted segmented prefix sum: x a list of ciphertexts (ints modulo n^2) read as [len(x) // seg_len][seg_len]
+        -> the list of as many ciphertexts prod_{u <= t} x[r][u] mod n^2 (reverse: u >= t), i.e. encryptions of the
+        inclusive cumulative sums mod n along every row.  One pgpu_batch_ct_segment_scan call on resident batches; there
+        is no element-wise fall-back."""
+        count, seg_len = len(x), int(seg_len)
+        if count == 0 or seg_len <= 0 or count % seg_len:
+            raise RuntimeError("segment scan error: seg_len must be positive and divide len(x)")
+        L = _capi.lib()
+        W = 2 * self.n_words
+        hx, ho = ctypes.c_void_p(), ctypes.c_void_p()
+        try:
+            xa = ints_to_limbs([int(v) for v in x], W)
+            _capi.check(L.pgpu_batch_upload(_ptr(xa), count, W, W, ctypes.byref(hx)))
+            _capi.check(L.pgpu_batch_ct_segment_scan(self._h, hx, seg_len, _capi.SCAN_REVERSE if reverse else 0, ctypes.byref(ho)))
+            out = np.empty((count, W), dtype=np.uint64)
+            _capi.check(L.pgpu_batch_download(ho, _ptr(out)))
+        finally:
+            for h in (hx, ho):
+                if h:
+                    L.pgpu_batch_destroy(h)
+        return limbs_to_ints(out)
+
 
 class PrivateKey:
     """Host-side mirror of ipcl::PrivateKey::decrypt (CRT path, pri_key.cpp:65-90,114-157)."""
