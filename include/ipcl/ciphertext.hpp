@@ -17,6 +17,7 @@ CipherText matVec(const PlainText& w, std::size_t rows, const CipherText& x);
 // include/ipcl/ext/aggregate.hpp
 CipherText segmentSum(const CipherText& x, const std::vector<uint32_t>& ids, std::size_t n_segments, std::size_t groups);
 CipherText segmentScan(const CipherText& x, std::size_t seg_len, bool reverse);
+CipherText packSlots(const CipherText& x, std::size_t seg_len, std::size_t slot_bits);
 }
 
 class CipherText : public BaseText {
@@ -52,6 +53,9 @@ class CipherText : public BaseText {
   friend CipherText ext::segmentScan(const CipherText& x, std::size_t seg_len, bool reverse);
   // prod_{u <= t} this[r][u] (reverse: u >= t), this read as [m_size / seg_len][seg_len]: csrc/host/aggregate.cpp
   CipherText segmentScanMap(std::size_t seg_len, bool reverse) const;
+  friend CipherText ext::packSlots(const CipherText& x, std::size_t seg_len, std::size_t slot_bits);
+  // prod_t this[r][t]^(2^(slot_bits t)), this read as [m_size / seg_len][seg_len]: csrc/host/aggregate.cpp
+  CipherText packMap(std::size_t seg_len, std::size_t slot_bits) const;
   CipherText(const PublicKey& pk, std::shared_ptr<detail::DeviceBatch> dev);
   CipherText(std::shared_ptr<PublicKey> pk, std::shared_ptr<detail::DeviceBatch> dev);
   std::shared_ptr<PublicKey> m_pk;

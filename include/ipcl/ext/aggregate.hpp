@@ -12,6 +12,17 @@
 //       (seg_len = n_segments), both sides of every split without a subtraction; a running total over one long vector
 //       with seg_len = x.getSize().  The scan is inclusive.  seg_len must be positive and divide x.getSize().
 //
+//   packSlots(x, seg_len, slot_bits)
+//       x read as [x.getSize() / seg_len][seg_len]; y[r] = sum_t x[r][t] * 2^(slot_bits t) under the encryption:
+//       Y[r] = prod_t X[r][t]^(2^(slot_bits t)) mod n^2 -- seg_len values of slot_bits bits in ONE ciphertext, slot 0 the
+//       least significant ("cipher compressing"): the key holder decrypts x.getSize() / seg_len ciphertexts instead of
+//       x.getSize().  seg_len must be positive and divide x.getSize(); seg_len * slot_bits must stay below the bits of n.
+//       A slot value of 2^slot_bits or more carries into its neighbour; headroom for sums taken after packing is the
+//       caller's choice of slot_bits.
+//   unpackSlots(m, seg_len, slot_bits)
+//       the way back after PrivateKey::decrypt: the m.getSize() * seg_len slot values in input order (host bit slicing,
+//       ipcl/ext/slots.hpp).  Throws when an element is negative or has bits beyond its last slot.
+//
 // ids: groups*cols plaintext segment numbers, row-major, each below n_segments or kSegmentNone (the element is left out
 // of that group: a missing value, a sample outside the node).  groups > 1 reads the same x once per group under another
 // grouping.  An empty segment yields the ciphertext 1 (it decrypts to 0).  One fused launch sequence on the GPU
@@ -28,6 +39,7 @@
 #include <vector>
 
 #include "ipcl/ciphertext.hpp"
+#include "ipcl/plaintext.hpp"
 
 namespace ipcl {
 namespace ext {
@@ -37,6 +49,8 @@ constexpr uint32_t kSegmentNone = 0xFFFFFFFFu;
 CipherText segmentSum(const CipherText& x, const std::vector<uint32_t>& ids, std::size_t n_segments,
                       std::size_t groups = 1);
 CipherText segmentScan(const CipherText& x, std::size_t seg_len, bool reverse = false);
+CipherText packSlots(const CipherText& x, std::size_t seg_len, std::size_t slot_bits);
+PlainText unpackSlots(const PlainText& m, std::size_t seg_len, std::size_t slot_bits);
 
 }  // namespace ext
 }  // namespace ipcl

@@ -373,6 +373,29 @@ int pgpu_batch_ct_segment_scan(const pgpu_pubkey* key, const pgpu_batch* x, size
  * PGPU_ERR_UNSUPPORTED: no pair rows for keys of key_bits.  PGPU_ERR_INVALID_PARAM: rows == 0, seg_len == 0, more chunks
  * than a 32-bit carry index addresses. */
 int pgpu_ct_segment_scan_plan(int key_bits, size_t rows, size_t seg_len, int* chunk, int* levels, size_t* products);
+/* Encrypted slot packing ("cipher compressing": pack before decrypt): x a resident ciphertext batch of count = rows *
+ * seg_len elements (pair rows, or uploaded plain ciphertext words: converted on the way in), read as [rows][seg_len]:
+ *     out[r] = prod_t x[r][t]^(2^(slot_bits * t)) mod n^2     i.e. Dec(out[r]) = sum_t Dec(x[r][t]) * 2^(slot_bits * t) mod n
+ * -- one ciphertext whose plaintext carries seg_len slots of slot_bits bits, slot 0 the least significant: the key holder
+ * decrypts rows ciphertexts where it decrypted count, and 1 / seg_len of the bytes travel.  The result is an ordinary
+ * resident ciphertext batch of rows elements in pair rows on the lane of x, usable by every other operation; x is left
+ * unchanged.  One launch, one Horner chain per row: (seg_len - 1) * (slot_bits + 1) pair products ("Encrypted
+ * slot packing"); seg_len == 1 is a copy (it converts, but runs no product).
+ * SLOTS: nothing here looks at the values.  A slot value of 2^slot_bits or more carries into its neighbour, exactly as in
+ * an integer sum; headroom for sums taken AFTER packing (pgpu_batch_ct_add of packed rows adds slot-wise) is the caller's
+ * choice of slot_bits: k packed rows added need slot_bits >= bits of a value + ceil(log2 k).
+ * PGPU_ERR_INVALID_PARAM: null / stale handles, seg_len == 0, count(x) % seg_len != 0, slot_bits < 1, seg_len * slot_bits
+ * > bitlen(n) - 1 (a pack that wraps modulo n is never meant), ciphertext width mismatch, a batch of another key.
+ * PGPU_ERR_UNSUPPORTED: keys without pair rows (beyond 3072 bits; PGPU_PAIR_ROWS=0 / PGPU_HENSEL=0), pools of more than one
+ * GPU, and the masked table-gather policy.  SIDE CHANNELS: the address stream of this call depends only on rows and
+ * seg_len; the refusal under pgpu_set_table_gather_policy(1) is kept so that one rule covers the aggregation calls.
+ * All refusals are decided on the host before any launch and leave *out untouched. */
+int pgpu_batch_ct_pack(const pgpu_pubkey* key, const pgpu_batch* x, size_t seg_len, int slot_bits, pgpu_batch** out);
+/* What a call of this shape would run (host-side query, needs no device).  lanes, limbs: the (G, K) form of the launch;
+ * products = rows * (seg_len - 1) * (slot_bits + 1).  The capacity bound is taken as key_bits - 1.
+ * PGPU_ERR_INVALID_PARAM: key_bits < 1, rows == 0, seg_len == 0, slot_bits < 1, seg_len * slot_bits > key_bits - 1, a product
+ * count beyond size_t.  PGPU_ERR_UNSUPPORTED: no pair rows for keys of key_bits. */
+int pgpu_ct_pack_plan(int key_bits, size_t rows, size_t seg_len, int slot_bits, int* lanes, int* limbs, size_t* products);
 
 /* ---- instrumentation used by bench.py (roofline) ----
  * With timing enabled every kernel launch is bracketed by two HIP events recorded on the stream
@@ -386,7 +409,8 @@ typedef enum pgpu_kernel_kind {
   PGPU_KERNEL_FB_ENCRYPT = 4, /* fb_encrypt_kernel (DJN encrypt, fixed-base) */
   PGPU_KERNEL_MATVEC = 5,     /* every launch of pgpu_batch_ct_matvec: table build, multi-exponentiation, fold */
   PGPU_KERNEL_SEGSUM = 6,     /* every launch of pgpu_batch_ct_segment_sum: one per level */
-  PGPU_KERNEL_SEGSCAN = 7     /* every launch of pgpu_batch_ct_segment_scan: up-sweeps (segsum_kernel) and scans */
+  PGPU_KERNEL_SEGSCAN = 7,    /* every launch of pgpu_batch_ct_segment_scan: up-sweeps (segsum_kernel) and scans */
+  PGPU_KERNEL_PACK = 8        /* the launch of pgpu_batch_ct_pack */
 } pgpu_kernel_kind;
 int pgpu_set_timing(int enabled);
 int pgpu_timing_collect(int* kinds, double* ms, int max_entries);

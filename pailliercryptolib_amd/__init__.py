@@ -5,5 +5,5 @@
 """
 from . import _capi  # noqa: F401
 from .engine import (initialize, terminate, mod_exp, mod_exp_limbs, mod_mul, mod_mul_limbs,  # noqa: F401
-                     PublicKey, PrivateKey)
+                     PublicKey, PrivateKey, unpack_slots)
 from .limbs import ints_to_limbs, limbs_to_ints  # noqa: F401

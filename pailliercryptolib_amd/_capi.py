@@ -38,6 +38,7 @@ SYMBOLS = [
     "pgpu_batch_ct_matvec", "pgpu_ct_matvec_plan",
     "pgpu_batch_ct_segment_sum", "pgpu_ct_segment_sum_plan",
     "pgpu_batch_ct_segment_scan", "pgpu_ct_segment_scan_plan",
+    "pgpu_batch_ct_pack", "pgpu_ct_pack_plan",
 ]
 FEATURE_4096_SPLIT = 1
 SEGMENT_NONE = 0xFFFFFFFF      # PGPU_SEGMENT_NONE: the element is left out of that group
@@ -181,6 +182,10 @@ def lib():
     L.pgpu_batch_ct_segment_scan.restype = c_int
     L.pgpu_ct_segment_scan_plan.argtypes = [c_int, c_size_t, c_size_t, POINTER(c_int), POINTER(c_int), POINTER(c_size_t)]
     L.pgpu_ct_segment_scan_plan.restype = c_int
+    L.pgpu_batch_ct_pack.argtypes = [c_void_p, c_void_p, c_size_t, c_int, POINTER(c_void_p)]
+    L.pgpu_batch_ct_pack.restype = c_int
+    L.pgpu_ct_pack_plan.argtypes = [c_int, c_size_t, c_size_t, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_size_t)]
+    L.pgpu_ct_pack_plan.restype = c_int
     _lib = L
     return L
 

@@ -949,6 +949,85 @@ int pgpu_batch_ct_segment_scan(const pgpu_pubkey* key, const pgpu_batch* x, size
   return PGPU_OK;
 }
 
+// ---- encrypted slot packing (hensel_pack.hpp) ----
+// seg_len * slot_bits <= cap, without forming the product
+static bool pack_fits(size_t seg_len, int slot_bits, int cap) {
+  return seg_len >= 1 && slot_bits >= 1 && cap >= 1 && slot_bits <= cap && seg_len <= (size_t)(cap / slot_bits);
+}
+
+int pgpu_ct_pack_plan(int key_bits, size_t rows, size_t seg_len, int slot_bits, int* lanes, int* limbs, size_t* products) {
+  if (key_bits < 1 || rows == 0 || seg_len == 0 || slot_bits < 1)
+    return fail(PGPU_ERR_INVALID_PARAM, "pack plan: key_bits, rows, seg_len and slot_bits must be positive");
+  if (!pack_fits(seg_len, slot_bits, key_bits - 1))
+    return fail(PGPU_ERR_INVALID_PARAM, "pack plan: seg_len * slot_bits exceeds key_bits - 1 (the packed plaintext would wrap modulo n)");
+  int G = 0, K = 0;
+  if (!policy::pack_geometry(key_bits, rows, &G, &K))
+    return fail(PGPU_ERR_UNSUPPORTED, "pack: keys of this size have no pair rows (1024- to 3072-bit key classes only)");
+  const size_t per_row = (seg_len - 1) * ((size_t)slot_bits + 1);   // (both factors are below key_bits)
+  if (per_row && rows > ~(size_t)0 / per_row) return fail(PGPU_ERR_INVALID_PARAM, "pack plan: the product count overflows");
+  if (lanes) *lanes = G;
+  if (limbs) *limbs = K;
+  if (products) *products = rows * per_row;
+  return PGPU_OK;
+}
+
+int pgpu_batch_ct_pack(const pgpu_pubkey* key, const pgpu_batch* x, size_t seg_len, int slot_bits, pgpu_batch** out) {
+  RC_TRY(rt::check_ready());
+  if (!key || !x || !out) return fail(PGPU_ERR_INVALID_PARAM, "null argument");
+  RC_TRY(check_gen(key->gen, "key"));
+  RC_TRY(check_gen(x->gen, "batch"));
+  const int W = 2 * key->n_words;
+  const size_t count = x->count;
+  if (seg_len == 0 || count == 0 || count % seg_len != 0)
+    return fail(PGPU_ERR_INVALID_PARAM, "pack error: seg_len must be positive and divide count(x)");
+  if (slot_bits < 1) return fail(PGPU_ERR_INVALID_PARAM, "pack error: slot_bits must be positive");
+  if (!pack_fits(seg_len, slot_bits, key->n.BitSize() - 1))
+    return fail(PGPU_ERR_INVALID_PARAM, "pack error: seg_len * slot_bits exceeds bitlen(n) - 1 (the packed plaintext would wrap modulo n)");
+  if (x->words != W) return fail(PGPU_ERR_INVALID_PARAM, "pack error: ciphertext width mismatch");
+  if (!same_domain(x->mont, key->nsq)) return fail(PGPU_ERR_INVALID_PARAM, "pack error: batch belongs to a different key");
+  if (rt::pool_size() > 1)
+    return fail(PGPU_ERR_UNSUPPORTED, "pack: pools of more than one GPU are not supported (rows are not sharded yet)");
+  const pgpu_pubkey::PubForm* pf = pair_form(key);
+  if (!pf || !pgpu::matvec_has(pf->H, pf->K))
+    return fail(PGPU_ERR_UNSUPPORTED, "pack: key has no pair form (1024- to 3072-bit keys; PGPU_PAIR_ROWS=0 / PGPU_HENSEL=0 switch it off)");
+  // the address stream here depends on rows and seg_len alone; the call is refused under the masked policy all the same,
+  // like its three siblings: one rule for the aggregation calls
+  if (g_ct_gather.load())
+    return fail(PGPU_ERR_UNSUPPORTED, "pack: the masked table-gather policy is on (pgpu_set_table_gather_policy / PGPU_CT_GATHER); "
+                                      "the aggregation calls on resident ciphertexts have no masked variant");
+  if (x->pair_l2 && (x->pair_l2 != pf->H * pf->K || !(x->pair_form->n == key->n)))
+    return fail(PGPU_ERR_INVALID_PARAM, "pack error: batch belongs to a different key");
+  const int G = pf->H, l2 = G * pf->K;
+  const size_t rows = count / seg_len;
+  std::unique_ptr<pgpu_batch> tx;
+  RC_TRY(as_pair_batch(key, x, &x, &tx));
+  std::unique_ptr<pgpu_batch> o;
+  RC_TRY(new_batch(rows, W, &o, l2, x->lane));
+  o->pair_form = pair_form_shared(key);
+  rt::Device& dev = rt::device(0);
+  rt::DeviceGuard g(dev.ordinal);
+  hipStream_t s = dev.bs(x->lane);
+  // the form with the same limbs per half on more lanes, for launches that leave SIMDs empty (policy.hpp: pack_wide_pays)
+  const pgpu_pubkey::PubForm* lf = pf;
+  for (const auto& alt : key->hforms)
+    if (alt->H * alt->K == l2 && alt->H > G && pgpu::pack_wide_has(alt->H, alt->K) && policy::pack_wide_pays(alt->H, rows)) lf = alt.get();
+  pgpu::PackArgs a{};
+  a.ctx = hensel_pub_view(lf, dev.index);
+  a.src = x->prow(0);
+  a.rows = rows;
+  a.seg_len = (uint32_t)seg_len;     // (both at most bitlen(n) - 1)
+  a.slot_bits = (uint32_t)slot_bits;
+  a.out = o->prow(0);
+  const size_t ipw = 64 / (size_t)lf->H, waves = (rows + ipw - 1) / ipw;
+  TimerScope t(dev, s, PGPU_KERNEL_PACK, PGPU_FORM_SEQ);
+  if (!pgpu::launch_pack(lf->H, lf->K, a, (unsigned)((waves + pgpu::kWavesPerWG - 1) / pgpu::kWavesPerWG), s))
+    return fail(PGPU_ERR_UNSUPPORTED, "pack kernels not compiled for this key class");
+  HIP_TRY(hipGetLastError());
+  t.stop();
+  *out = o.release();
+  return PGPU_OK;
+}
+
 int pgpu_set_batch_lane(int lane) {
   if (lane < 0 || lane >= rt::kBatchLanes) return fail(PGPU_ERR_INVALID_PARAM, "batch lane out of range (pgpu_batch_lanes())");
   t_batch_lane = lane;

@@ -1,5 +1,5 @@
 // pailliercryptolib_amd -- instantiations of the split-form CRT-decrypt exponentiation (hensel.hpp), split over
-// PGPU_PART = 0..47 so that they compile in parallel (38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 45-47: the encrypted segmented prefix sum; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
+// PGPU_PART = 0..51 so that they compile in parallel (38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 45-47: the encrypted segmented prefix sum; 48-51: the encrypted slot packing; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
 // the two-wavefronts-per-SIMD build of the (2,19) decrypt form; 11-13: element-wise operations on pair rows).
 #include "hensel_seq.hpp"
 #include "launch.hpp"
@@ -21,9 +21,12 @@
 #if defined(PGPU_PART) && PGPU_PART >= 45 && PGPU_PART <= 47
 #include "hensel_segscan.hpp"   // the encrypted segmented prefix sum: one product chain per chunk, every step stored
 #endif
+#if defined(PGPU_PART) && PGPU_PART >= 48 && PGPU_PART <= 51
+#include "hensel_pack.hpp"      // the encrypted slot packing: one Horner chain per output row
+#endif
 
 #ifndef PGPU_PART
-#error "compile with -DPGPU_PART=0..47 (15 and 30 are retired)"
+#error "compile with -DPGPU_PART=0..51 (15 and 30 are retired)"
 #endif
 
 namespace pgpu {
@@ -506,6 +509,30 @@ bool PGPU_SS_NAME(int G, int K, const SegsumArgs& a, unsigned blocks, hipStream_
 bool PGPU_SC_NAME(int G, int K, const SegscanArgs& a, unsigned blocks, hipStream_t s) {
   if (G != PGPU_SC_G || K != PGPU_SC_K) return false;
   hipLaunchKernelGGL((segscan_kernel<PGPU_SC_G, PGPU_SC_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
+  return true;
+}
+#elif PGPU_PART >= 48 && PGPU_PART <= 51
+// the encrypted slot packing (hensel_pack.hpp): one geometry per part
+#if PGPU_PART == 48
+#define PGPU_PK_G 4
+#define PGPU_PK_K 18
+#define PGPU_PK_NAME launch_pack_part48
+#elif PGPU_PART == 49
+#define PGPU_PK_G 8
+#define PGPU_PK_K 14
+#define PGPU_PK_NAME launch_pack_part49
+#elif PGPU_PART == 50
+#define PGPU_PK_G 2
+#define PGPU_PK_K 19
+#define PGPU_PK_NAME launch_pack_part50
+#else
+#define PGPU_PK_G 8
+#define PGPU_PK_K 9
+#define PGPU_PK_NAME launch_pack_part51
+#endif
+bool PGPU_PK_NAME(int G, int K, const PackArgs& a, unsigned blocks, hipStream_t s) {
+  if (G != PGPU_PK_G || K != PGPU_PK_K) return false;
+  hipLaunchKernelGGL((pack_kernel<PGPU_PK_G, PGPU_PK_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
   return true;
 }
 #else

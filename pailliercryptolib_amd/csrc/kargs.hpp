@@ -354,6 +354,20 @@ struct SegscanArgs {
   int step;                  // +1: prefix products, -1: suffix products
 };
 
+// Encrypted slot packing on pair rows (hensel_pack.hpp): src read as [rows][seg_len], one Horner chain per row,
+//     out[r] = prod_t src[r][t]^(2^(slot_bits * t)):  slot 0 the least significant, one row stored per chain.
+// No descriptors: every chain of a launch has the same trip count.  The host keeps seg_len * slot_bits below the bit
+// length of n, so both fit 32 bits.  The stored row comes out of seq_pairmul (or is the input row itself when seg_len
+// == 1): a valid operand for every consumer of pair rows.
+struct PackArgs {
+  HenselPubDev ctx;
+  const uint32_t* src;       // [rows * seg_len][2*L2] pair rows
+  size_t rows;               // >= 1
+  uint32_t seg_len;          // >= 1
+  uint32_t slot_bits;        // >= 1
+  uint32_t* out;             // [rows][2*L2], never the same memory as src
+};
+
 struct FixedBaseArgs {
   ModCtxDev ctx;         // modulus n^2 (nr set)
   const uint32_t* table; // [nwin][2^w][L]

@@ -334,6 +334,19 @@ inline bool launch_segscan(int G, int K, const SegscanArgs& a, unsigned blocks, 
          launch_segscan_part47(G, K, a, blocks, s);
 }
 
+// The encrypted slot packing (hensel_pack.hpp; k_hensel.hip parts 48-51): one Horner chain per output row, in the
+// geometries matvec_has lists, and -- part 51 -- with the 72 limbs of a 2048-bit key's half on 8 lanes instead of 4 (the
+// same pair rows, half the serial time per product, half the chains per wavefront): launches that leave SIMDs empty
+inline bool pack_wide_has(int G, int K) { return G == 8 && K == 9; }
+bool launch_pack_part48(int G, int K, const PackArgs& a, unsigned blocks, hipStream_t s);
+bool launch_pack_part49(int G, int K, const PackArgs& a, unsigned blocks, hipStream_t s);
+bool launch_pack_part50(int G, int K, const PackArgs& a, unsigned blocks, hipStream_t s);
+bool launch_pack_part51(int G, int K, const PackArgs& a, unsigned blocks, hipStream_t s);
+inline bool launch_pack(int G, int K, const PackArgs& a, unsigned blocks, hipStream_t s) {
+  return launch_pack_part48(G, K, a, blocks, s) || launch_pack_part49(G, K, a, blocks, s) ||
+         launch_pack_part50(G, K, a, blocks, s) || launch_pack_part51(G, K, a, blocks, s);
+}
+
 // DJN encrypt to pair rows in the same form (k_hensel.hip parts 20, 21, 28): (4,18) 2048-bit keys, (8,14) 3072, (2,19) 1024
 inline bool hensel_fb_encrypt_seq_has(int G, int K) { return (G == 4 && K == 18) || (G == 8 && K == 14) || (G == 2 && K == 19); }
 bool launch_hensel_fb_encrypt_seq_part28(int G, int K, const HenselFbArgs& a, unsigned blocks, hipStream_t s);

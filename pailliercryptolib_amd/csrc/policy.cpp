@@ -375,5 +375,25 @@ void segscan_plan(size_t rows, size_t seg_len, int chunk, bool reverse, SegscanP
   }
 }
 
+
+// ---- encrypted slot packing ----
+bool pack_wide_pays(int wide_G, size_t rows) {
+  const char* e = std::getenv("PGPU_PACK_WIDE");     // (unset is not 0 here: both values force)
+  if (e && (e[0] == '0' || e[0] == '1') && !e[1]) return e[0] == '1';
+  return segsum_wide_pays(wide_G, rows);
+}
+bool pack_geometry(int key_bits, size_t rows, int* G, int* K) {
+  int g = 0, k = 0;
+  if (!matvec_geometry(key_bits, &g, &k)) return false;
+  // the form with the same limbs per half on twice the lanes, where one is compiled (capi_keys.inc builds it for such keys)
+  if (k % 2 == 0 && pgpu::pack_wide_has(2 * g, k / 2) && pack_wide_pays(2 * g, rows)) {
+    g *= 2;
+    k /= 2;
+  }
+  if (G) *G = g;
+  if (K) *K = k;
+  return true;
+}
+
 }  // namespace policy
 }  // namespace pgpu

@@ -201,6 +201,21 @@ struct SegscanPlan {
 };
 void segscan_plan(size_t rows, size_t seg_len, int chunk, bool reverse, SegscanPlan* plan);
 
+
+// ---- the encrypted slot packing (hensel_pack.hpp; pgpu_batch_ct_pack, pgpu_ct_pack_plan) ----
+// One Horner chain of (seg_len - 1) * (slot_bits + 1) products per output row, one launch, every chain equally long: there
+// is no plan but the form.  The rows are few by construction (count / seg_len), and a launch whose wavefronts leave SIMDs
+// empty costs by the depth of one chain: such a launch runs in the form with the same limbs per half on wide_G > G lanes
+// (2048-bit keys: (8,9) beside (4,18); launch.hpp: pack_wide_has) -- the same rows, half the serial time per product --
+// when even 64 / wide_G chains per wavefront put at most one wavefront on a SIMD (segsum_wide_pays' rule: up to 8192 rows).
+// The rule is carried over from the segmented sum; measured: the wide form takes 0.80 of the base
+// form's time at 64 and 2048 rows, 0.82 at 8192, 1.33 at 16384 and 1.29 at 32768; nothing was measured between 8192
+// and 16384 rows, so the switch at 8192 is on the right side of both neighbours and not located more finely.
+// PGPU_PACK_WIDE=0 / 1 forces the base / the wide form where the key has one (read at every call: the measurement).
+bool pack_wide_pays(int wide_G, size_t rows);
+// the (G, K) form a call over `rows` output rows launches for keys of key_bits; false: no pair rows for such keys
+bool pack_geometry(int key_bits, size_t rows, int* G, int* K);
+
 }  // namespace policy
 }  // namespace pgpu
 

@@ -231,6 +231,54 @@ class PublicKey:
                     L.pgpu_batch_destroy(h)
         return limbs_to_ints(out)
 
+    def pack(self, x, seg_len, slot_bits):
+        """Encrypted slot packing: x a list of ciphertexts (ints modulo n^2) read as [len(x) // seg_len][seg_len] -> the
+        list of len(x) // seg_len ciphertexts prod_t x[r][t]^(2^(slot_bits * t)) mod n^2, i.e. encryptions of
+        sum_t m[r][t] * 2^(slot_bits * t) mod n: seg_len slots of slot_bits bits per plaintext, slot 0 the least
+        significant (unpack_slots takes the decrypted values apart).  One pgpu_batch_ct_pack call on resident batches;
+        there is no element-wise fall-back."""
+        count, seg_len, slot_bits = len(x), int(seg_len), int(slot_bits)
+        if count == 0 or seg_len <= 0 or count % seg_len:
+            raise RuntimeError("pack error: seg_len must be positive and divide len(x)")
+        if not 1 <= slot_bits <= 1 << 30:
+            raise RuntimeError("pack error: slot_bits must be positive")
+        L = _capi.lib()
+        W = 2 * self.n_words
+        hx, ho = ctypes.c_void_p(), ctypes.c_void_p()
+        try:
+            xa = ints_to_limbs([int(v) for v in x], W)
+            _capi.check(L.pgpu_batch_upload(_ptr(xa), count, W, W, ctypes.byref(hx)))
+            _capi.check(L.pgpu_batch_ct_pack(self._h, hx, seg_len, slot_bits, ctypes.byref(ho)))
+            out = np.empty((count // seg_len, W), dtype=np.uint64)
+            _capi.check(L.pgpu_batch_download(ho, _ptr(out)))
+        finally:
+            for h in (hx, ho):
+                if h:
+                    L.pgpu_batch_destroy(h)
+        return limbs_to_ints(out)
+
+
+def unpack_slots(ms, seg_len, slot_bits, width_bits=None):
+    """The way back from PublicKey.pack, after decrypt: every plaintext of ms holds seg_len slots of slot_bits bits, slot 0
+    the least significant -> the len(ms) * seg_len slot values in input order (ms[0]'s slots first).  Pure host bit
+    slicing; a slot that overflowed before the decrypt has carried into its neighbour and cannot be told apart here.
+    width_bits: the width of the plaintexts (the bits of n, less one) when the caller wants the capacity checked too.
+    ValueError: non-positive seg_len or slot_bits, seg_len * slot_bits above width_bits, a negative plaintext or one with
+    bits beyond the last slot."""
+    seg_len, slot_bits = int(seg_len), int(slot_bits)
+    if seg_len <= 0 or slot_bits <= 0:
+        raise ValueError("unpack_slots: seg_len and slot_bits must be positive")
+    if width_bits is not None and seg_len * slot_bits > int(width_bits):
+        raise ValueError("unpack_slots: seg_len * slot_bits exceeds the plaintext width")
+    mask = (1 << slot_bits) - 1
+    out = []
+    for m in ms:
+        m = int(m)
+        if m < 0 or m >> (seg_len * slot_bits):
+            raise ValueError("unpack_slots: a plaintext does not fit seg_len slots of slot_bits bits")
+        out.extend((m >> (slot_bits * t)) & mask for t in range(seg_len))
+    return out
+
 
 class PrivateKey:
     """Host-side mirror of ipcl::PrivateKey::decrypt (CRT path, pri_key.cpp:65-90,114-157)."""
