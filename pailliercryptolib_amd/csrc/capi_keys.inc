@@ -79,15 +79,10 @@ int build_hensel_pub_form(pgpu_pubkey* k, int H, int K) {
   return PGPU_OK;
 }
 int build_hensel_pub(pgpu_pubkey* k) {
-  const int need = k->n.BitSize() + 29 + 8;
-  const int nsq_bits = 2 * k->n.BitSize();
-  for (int H : {8, 4, 2})
-    for (int K = 1; K <= 19; ++K)
-      if ((pgpu::hensel_modexp_has(H, K) || pgpu::hensel_fb_has(H, K)) && pgpu::kLimbBits * H * K >= need &&
-          2 * pgpu::kLimbBits * H * K >= nsq_bits + 8) {
-        RC_TRY(build_hensel_pub_form(k, H, K));
-        break;
-      }
+  // which forms, and in which order (the pair form of the key last: pair_form, use_split_encrypt): policy.hpp
+  std::vector<std::pair<int, int>> forms;
+  policy::pub_forms_for_bits(k->n.BitSize(), &forms);
+  for (const auto& f : forms) RC_TRY(build_hensel_pub_form(k, f.first, f.second));
   return PGPU_OK;
 }
 }  // namespace
@@ -127,20 +122,13 @@ void pgpu_pubkey_destroy(pgpu_pubkey* key) { delete key; }
 namespace {
 // Constants of the split-form exponentiation (hensel.hpp) for both sides of the key.  A residue z modulo P^2 is
 // the pair (a, b) with z == a - P*b: a = z mod P, b = (P - z div P) mod P.
-// limbs per half of the pair rows a PUBLIC key over n would use (build_hensel_pub: its form of fewest lanes), 0: none
+// limbs per half of the pair rows a PUBLIC key over n uses (policy.hpp: pair_form_for_bits, as build_hensel_pub), 0: none
 int pair_l2_for_modulus(const BigNumber& n, int* H_out = nullptr, int* K_out = nullptr) {
-  const int need = n.BitSize() + 29 + 8, nsq_bits = 2 * n.BitSize();
-  int l2 = 0;
-  for (int H : {8, 4, 2})
-    for (int K = 1; K <= 19; ++K)
-      if ((pgpu::hensel_modexp_has(H, K) || pgpu::hensel_fb_has(H, K)) && pgpu::kLimbBits * H * K >= need &&
-          2 * pgpu::kLimbBits * H * K >= nsq_bits + 8) {
-        l2 = pgpu::pair_ops_has(H, K) ? H * K : 0;
-        if (H_out) *H_out = H;
-        if (K_out) *K_out = K;
-        break;
-      }
-  return l2;
+  int H = 0, K = 0;
+  if (!policy::pair_form_for_bits(n.BitSize(), &H, &K)) return 0;
+  if (H_out) *H_out = H;
+  if (K_out) *K_out = K;
+  return H * K;
 }
 
 int build_hensel_set(pgpu_privkey* k, pgpu_privkey::HenselSet* hs, int H, int K, const BigNumber& p,

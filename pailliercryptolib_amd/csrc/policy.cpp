@@ -186,18 +186,48 @@ static long env_now(const char* name) {
   const char* e = std::getenv(name);
   return e && *e ? std::atol(e) : 0;
 }
-bool matvec_geometry(int key_bits, int* G, int* K) {
-  // the rule of build_hensel_pub (capi_keys.inc) for the form of fewest lanes: 29 * G * K >= bits of n + 29 + 8
-  static const int forms[3][2] = {{2, 19}, {4, 18}, {8, 14}};
-  if (key_bits < 1) return false;
+bool pair_form_for_bits(int n_bits, int* G, int* K) {
+  // R = 2^(29 G K) >= 2^8 P with P = n k < 2^(bits + 29); from fewest lanes to most, and of one lane count the fewest limbs
+  static const int forms[4][2] = {{2, 19}, {4, 18}, {8, 14}, {8, 18}};
+  if (n_bits < 1) return false;
   for (const auto& f : forms) {
-    if (pgpu::kLimbBits * f[0] * f[1] >= key_bits + pgpu::kLimbBits + 8 && pgpu::matvec_has(f[0], f[1])) {
+    if (pgpu::kLimbBits * f[0] * f[1] >= n_bits + pgpu::kLimbBits + 8 && pgpu::pair_ops_has(f[0], f[1])) {
       if (G) *G = f[0];
       if (K) *K = f[1];
       return true;
     }
   }
   return false;
+}
+bool pair_wide_form(int G, int K, int* wide_G, int* wide_K) {
+  if (K % 2 != 0 || !pgpu::pair_ops_alt_has(2 * G, K / 2)) return false;
+  if (wide_G) *wide_G = 2 * G;
+  if (wide_K) *wide_K = K / 2;
+  return true;
+}
+void pub_forms_for_bits(int n_bits, std::vector<std::pair<int, int>>* forms) {
+  forms->clear();
+  if (n_bits < 1) return;
+  const int need = n_bits + pgpu::kLimbBits + 8, nsq_bits = 2 * n_bits;
+  int PG = 0, PK = 0, WG = 0, WK = 0;
+  const bool has_pair = pair_form_for_bits(n_bits, &PG, &PK);
+  const bool has_wide = has_pair && pair_wide_form(PG, PK, &WG, &WK);
+  for (int H : {8, 4, 2})
+    for (int K = 1; K <= 19; ++K)
+      if ((pgpu::hensel_modexp_has(H, K) || pgpu::hensel_fb_has(H, K)) && pgpu::kLimbBits * H * K >= need &&
+          2 * pgpu::kLimbBits * H * K >= nsq_bits + 8) {
+        if (!(has_pair && H == PG && K == PK) && !(has_wide && H == WG && K == WK)) forms->push_back({H, K});
+        break;
+      }
+  if (has_wide) forms->push_back({WG, WK});
+  if (has_pair) forms->push_back({PG, PK});
+}
+bool matvec_geometry(int key_bits, int* G, int* K) {
+  int g = 0, k = 0;
+  if (!pair_form_for_bits(key_bits, &g, &k) || !pgpu::matvec_has(g, k)) return false;
+  if (G) *G = g;
+  if (K) *K = k;
+  return true;
 }
 size_t matvec_slices(int G, size_t rows, size_t cols) {
   if (rows == 0 || cols == 0) return 1;

@@ -16,6 +16,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <utility>
 #include <vector>
 
 #include "kargs.hpp"
@@ -80,6 +81,31 @@ int pick_decrypt_window(int exp_bits, size_t entry_bytes = 0);
 int masked_decrypt_window();
 
 
+// ---- the pair form of a key: the ONE rule from the bit length of n to the (G, K) form of its resident pair rows ----
+// The form of fewest lanes among those with element-wise kernels (launch.hpp: pair_ops_has) whose radix leaves the lazy
+// bounds their room: R = 2^(29 G K) >= 2^8 P for the loop modulus P = n k < 2^(bits + 29), i.e. 29 G K >= bits + 29 + 8.
+// The key builders (capi_keys.inc: build_hensel_pub for a public key, pair_l2_for_modulus for a private one) and the plan
+// calls (matvec_geometry, pack_geometry) all ask this function; tests/cpp/key_width_policy_tests.cpp sweeps it.
+//     bits of n      form     limbs per half (a row is twice that)
+//        1 .. 1065   (2,19)    38
+//     1066 .. 2051   (4,18)    72    -- also 1066 .. 1123, whose smallest 4-lane modexp form (4,10) has no pair kernels
+//     2052 .. 3211   (8,14)   112
+//     3212 .. 4139   (8,18)   144    only in builds with PGPU_WITH_4096; else none
+//     wider                   none: every resident operation runs on word rows, the aggregation calls refuse
+bool pair_form_for_bits(int n_bits, int* G, int* K);
+// the form with the same limbs per half on twice the lanes that small launches take beside (G, K) -- (8,9) beside (4,18):
+// element-wise operations, DJN encrypt, segment_sum, pack (launch.hpp: pair_ops_alt_has, hensel_fb_encrypt_has,
+// segsum_wide_has, pack_wide_has); a key with pair form (G, K) carries its constants too.  false: none compiled
+bool pair_wide_form(int G, int K, int* wide_G, int* wide_K);
+// every split form of n^2 a public key over an n of n_bits bits builds constants for (capi_keys.inc: build_hensel_pub), in
+// the order of its list: per lane count 8, 4, 2 the smallest compiled form (fixed-base or generic modexp kernel) with
+// 29 H K >= bits + 29 + 8 -- the forms of one-shot operations on host words, most lanes first --, then the wide form, then
+// the pair form LAST: the list's back() is what defines the key's resident rows.  For most widths the last two are what
+// the per-lane-count search finds anyway; keys of 1066 .. 1123 bits, whose smallest 4- and 8-lane forms (4,10) and (8,5)
+// have no pair kernels, receive (8,9) and (4,18) in addition.  Empty: no split form (word rows everywhere).
+void pub_forms_for_bits(int n_bits, std::vector<std::pair<int, int>>* forms);
+
+
 // ---- the encrypted matrix-vector product (hensel_matvec.hpp; pgpu_batch_ct_matvec, pgpu_ct_matvec_plan) ----
 // Y[i] = prod_j X[j]^W[i][j] as an interleaved fixed-window multi-exponentiation: window tables of the cols ciphertexts
 // shared by all rows, one group of G lanes per (row, column slice).  Counted in pair products a call costs
@@ -87,8 +113,9 @@ int masked_decrypt_window();
 //   + rows * S * e_bits               squarings (every slice runs its own chain)
 //   + rows * cols * ceil(e_bits / w)  multiplications by table entries
 //   + rows * (S - 1)                  fold of the partial products.
-// Geometry of the key class (the sequential-halves forms of hensel_modexp_seq_kernel): (2,19) up to 1065-bit n, (4,18) up
-// to 2051, (8,14) up to 3211; false: the class has no pair rows (4096-bit keys).
+// Geometry of the key class: its pair form (pair_form_for_bits) where the aggregation kernels are compiled for it
+// (launch.hpp: matvec_has -- the sequential-halves forms of hensel_modexp_seq_kernel): (2,19) up to 1065-bit n, (4,18) up
+// to 2051, (8,14) up to 3211; false: no pair rows (wider keys), or pair rows without these kernels ((8,18), 4096-bit builds).
 bool matvec_geometry(int key_bits, int* G, int* K);
 // S: the smallest slice count that puts a wavefront on every SIMD -- a wavefront holds 64/G rows of one slice -- but a
 // slice keeps at least kMatvecMinSliceCols columns, so that the e_bits squarings every slice repeats stay at most
