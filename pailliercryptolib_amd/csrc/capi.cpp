@@ -663,6 +663,9 @@ struct pgpu_privkey {
   // the constants of hensel_decrypt_ps_kernel (hensel_ps.hpp: one lane per exponentiation, product scanning): H = 1,
   // K limbs of lb bits per half (2048-bit keys: 38 x 28); null: no such kernel for this key size
   std::unique_ptr<HenselSet> hs_ps;
+  // the same on balanced limbs (hensel_ps_bal.hpp: 36 x 29 for the 2048-bit class, P = p): what the one-lane kernel reads
+  // unless PGPU_PS_BALANCED=0; null: the primes do not fit or no such kernel.  The policy keeps deciding by hs_ps
+  std::unique_ptr<HenselSet> hs_psb;
   // constants of the pair rows of n^2 = (p*q)^2 -- what a public key over n holds as its pair form: word ciphertexts are
   // brought into pair rows with it when the launch then takes a kernel that reads only those (decrypt_on)
   std::shared_ptr<pgpu_pubkey::PubForm> conv_form;
@@ -1727,6 +1730,12 @@ int host_busy(rt::Device& dev, int lane, size_t count = (size_t)-1) {
   return busy >= k ? busy : 0;
 }
 
+// PGPU_PS_BALANCED (default 1): the one-lane form runs on balanced limbs where the key has such a set (hensel_ps_bal.hpp);
+// 0 brings hensel_decrypt_ps_kernel of the unsigned set back
+std::atomic<int> g_ps_balanced{[] { const char* e = std::getenv("PGPU_PS_BALANCED"); return e && std::atoi(e) == 0 ? 0 : 1; }()};
+const pgpu_privkey::HenselSet* ps_balanced_set(const pgpu_privkey* key, int pair_l2) {
+  return (g_ps_balanced.load() && key->hs_psb && key->hs_psb->pair_l2 == pair_l2) ? key->hs_psb.get() : nullptr;
+}
 // the one-lane product-scanning form (csrc/hensel_ps.hpp) for a decrypt of `count` resident ciphertexts under this key?
 bool ps_form_pays(const pgpu_privkey* key, size_t count, int busy) {
   return key->hs_ps && hensel_enabled() && policy::ps_form_pays(count, busy, key->hs_ps->K);
@@ -1778,6 +1787,8 @@ int decrypt_on(rt::Device& d, const pgpu_privkey* key, const uint64_t* d_c, uint
   const bool psf = wavef || (d_pair && !sliding && hset && ps_form_pays(key, count, busy_lanes) &&
                              key->hs_ps->pair_l2 == in_pair_l2);
   if (psf) hset = key->hs_ps.get();
+  const pgpu_privkey::HenselSet* bset = (psf && !wavef) ? ps_balanced_set(key, in_pair_l2) : nullptr;
+  if (bset) hset = bset;
   if (d_pair && (!hset || hset->pair_l2 != in_pair_l2))
     return fail(PGPU_ERR_UNSUPPORTED, "decrypt: pair-row ciphertexts need the split-form kernel of this key size");
   if (hset) {
@@ -1865,7 +1876,8 @@ int decrypt_on(rt::Device& d, const pgpu_privkey* key, const uint64_t* d_c, uint
       // spread over the chip, one wavefront per SIMD each)
       const unsigned lds_pad = adaptive_cu_claim(lwaves, busy_lanes);
       if (lds_pad) t.set_form(PGPU_FORM_LANE | PGPU_FORM_PS | PGPU_FORM_CU_CLAIM);
-      if (!pgpu::launch_hensel_ps(hset->K, hset->lb, h, lblocks, s, lds_pad))
+      if (bset ? !pgpu::launch_hensel_psb(hset->K, hset->lb, h, lblocks, s, lds_pad)
+               : !pgpu::launch_hensel_ps(hset->K, hset->lb, h, lblocks, s, lds_pad))
         return fail(PGPU_ERR_UNSUPPORTED, "one-lane product-scanning decrypt kernel not compiled");
     } else if (seq) {
       const unsigned sblocks = (unsigned)((seq_waves + pgpu::kWavesPerWG - 1) / pgpu::kWavesPerWG);
@@ -2336,8 +2348,12 @@ int pgpu_ct_add_kernel_form(const pgpu_pubkey* key, size_t count, int* split, in
   return PGPU_OK;
 }
 
+// (limbs of the one-lane form: the key's product-scanning CLASS, the limb count of its unsigned set, whichever set the
+// kernel reads; pgpu_decrypt_kernel_form_ex names the kernel that runs -- 36 on balanced limbs)
 int pgpu_decrypt_kernel_form(const pgpu_privkey* key, size_t count, int* split, int* lanes, int* limbs) {
-  return pgpu_decrypt_kernel_form_ex(key, count, 0, split, lanes, limbs);
+  RC_TRY(pgpu_decrypt_kernel_form_ex(key, count, 0, split, lanes, limbs));
+  if (*split == 4 && key->hs_ps) *limbs = key->hs_ps->K;
+  return PGPU_OK;
 }
 int pgpu_decrypt_kernel_form_ex(const pgpu_privkey* key, size_t count, int busy_lanes, int* split, int* lanes, int* limbs) {
   if (!key || !split || !lanes || !limbs) return fail(PGPU_ERR_INVALID_PARAM, "pgpu_decrypt_kernel_form: bad argument");
@@ -2354,7 +2370,8 @@ int pgpu_decrypt_kernel_form_ex(const pgpu_privkey* key, size_t count, int busy_
         key->hs_ps->pair_l2 == f->pair_l2) {
       *split = 4;
       *lanes = 1;
-      *limbs = key->hs_ps->K;
+      const pgpu_privkey::HenselSet* bal = ps_balanced_set(key, f->pair_l2);
+      *limbs = bal ? bal->K : key->hs_ps->K;
       return PGPU_OK;
     }
     if (pair_rows_enabled() && secret_policy() != PGPU_EXP_SLIDING && seq_form_pays(f->H, f->K, count, busy_lanes)) {
@@ -2420,6 +2437,8 @@ void pgpu_debug_set_ps_decrypt(int policy) { pgpu::policy::set_ps_policy(policy)
 void pgpu_debug_set_wave_decrypt(int policy) { pgpu::policy::set_wave_policy(policy); }
 int pgpu_debug_get_wave_decrypt(void) { return pgpu::policy::wave_policy(); }
 int pgpu_debug_get_ps_decrypt(void) { return pgpu::policy::ps_policy(); }
+// tests / A-B measurements: the one-lane form on balanced limbs (hensel_ps_bal.hpp) 1, on the unsigned set 0; returns what was set
+int pgpu_debug_set_ps_balanced(int on) { return g_ps_balanced.exchange(on != 0 ? 1 : 0); }
 // tests / A-B measurements: from how many active neighbour lanes on threads on round-robin lanes take the adaptive forms (0 never)
 int pgpu_debug_set_rr_adapt(int min_busy) { return pgpu::policy::set_rr_adapt(min_busy); }
 

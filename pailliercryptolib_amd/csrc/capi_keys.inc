@@ -132,12 +132,25 @@ int pair_l2_for_modulus(const BigNumber& n, int* H_out = nullptr, int* K_out = n
 }
 
 int build_hensel_set(pgpu_privkey* k, pgpu_privkey::HenselSet* hs, int H, int K, const BigNumber& p,
-                     const BigNumber& q, const BigNumber& hp, const BigNumber& hq, int lb = pgpu::kLimbBits) {
+                     const BigNumber& q, const BigNumber& hp, const BigNumber& hq, int lb = pgpu::kLimbBits,
+                     bool balanced = false) {
   // lb: bits per limb of the constants (R = 2^(lb*L2), P = prime * (-prime^-1 mod 2^lb)); the pair rows this set reads are
   // rows of 29-bit limbs in any case
+  // balanced (hensel_ps_bal.hpp): k = 1 -- P is the prime itself, n0inv its true -p^-1 mod 2^lb -- and every constant, the
+  // same value in [0, prime) and the same sign convention z = a - P*b of the pairs, is written in BALANCED limbs
+  // (two's complement words in [-2^(lb-1), 2^(lb-1)))
   const int L2 = H * K;
   const uint32_t lmask = (1u << lb) - 1;
-  auto to_limbs29 = [lb](const BigNumber& v, int L, uint32_t* out) { to_limbs(v, L, out, lb); };   // (shadows the 29-bit one)
+  auto to_limbs29 = [lb, balanced](const BigNumber& v, int L, uint32_t* out) {   // (shadows the 29-bit one)
+    to_limbs(v, L, out, lb);
+    if (!balanced) return;
+    uint32_t c = 0;
+    for (int j = 0; j < L; ++j) {       // (values are below 2^(lb*L - 4): the carry dies below the top limb)
+      const uint32_t u = out[j] + c;
+      c = u >= (1u << (lb - 1)) ? 1u : 0u;
+      out[j] = c ? u - (1u << lb) : u;
+    }
+  };
   hs->lb = lb;
   const int bits_lo = std::min(p.BitSize(), q.BitSize());
   // a ciphertext enters in chunks z < 2^(64*cw) <= 2P (P >= prime > 2^(bits-1))
@@ -173,7 +186,8 @@ int build_hensel_set(pgpu_privkey* k, pgpu_privkey::HenselSet* hs, int H, int K,
     uint32_t n0 = (uint32_t)(pr.limbs64()[0] & lmask), inv = n0;
     for (int i = 0; i < 5; ++i) inv *= 2u - n0 * inv;
     const uint32_t n0inv = (0u - inv) & lmask;
-    const BigNumber P = pr * BigNumber((Ipp32u)n0inv);
+    const BigNumber kfac((Ipp32u)(balanced ? 1u : n0inv));     // P = prime * k
+    const BigNumber P = pr * kfac;
     const BigNumber P2 = P * P;
     uint32_t* b = h.data() + sd * side_words;
     auto put_pair = [&](uint32_t* dst, const BigNumber& z) {
@@ -185,7 +199,7 @@ int build_hensel_set(pgpu_privkey* k, pgpu_privkey::HenselSet* hs, int H, int K,
     to_limbs29(P, L2, b);
     to_limbs29(pr, L2, b + L2);
     to_limbs29(sd ? hq : hp, L2, b + 2 * L2);
-    to_limbs29((R % pr) * BigNumber((Ipp32u)n0inv) % pr, L2, b + 3 * L2);   // P = prime * (-prime^-1 mod 2^29)
+    to_limbs29((R % pr) * kfac % pr, L2, b + 3 * L2);   // P = prime * (-prime^-1 mod 2^29)
     const BigNumber Rm = R % P2, R2 = (Rm * Rm) % P2;
     put_pair(b + 4 * L2, Rm);
     const BigNumber R2m = (R2 * P2.InverseMul(pow2(k->nsq_rbits) % P2)) % P2;   // cancels the R of the n^2 context
@@ -200,7 +214,7 @@ int build_hensel_set(pgpu_privkey* k, pgpu_privkey::HenselSet* hs, int H, int K,
       const BigNumber Rn = pow2(hs->pair_l2 * pgpu::kLimbBits);
       const BigNumber R2n = (R2 * P2.InverseMul(Rn % P2)) % P2;            // R^2 * Rn^-1 mod P^2
       const BigNumber other = sd ? p : q;
-      const BigNumber kinv = pr.InverseMul(BigNumber((Ipp32u)n0inv) % pr);   // k^-1 mod pr
+      const BigNumber kinv = pr.InverseMul(kfac % pr);   // k^-1 mod pr
       const BigNumber kappa = (((other % pr) * (BigNumber((Ipp32u)kn) % pr)) % pr * kinv) % pr;
       const BigNumber Rp = R % pr;
       const BigNumber r2n_p = (((Rp * Rp) % pr) * pr.InverseMul(Rn % pr)) % pr;   // R^2 * Rn^-1 mod pr
@@ -249,6 +263,16 @@ int build_hensel(pgpu_privkey* k, const BigNumber& p, const BigNumber& q, const 
           std::unique_ptr<pgpu_privkey::HenselSet> set(new pgpu_privkey::HenselSet);
           RC_TRY(build_hensel_set(k, set.get(), 1, K, p, q, hp, hq, lb));
           if (set->H && set->pair_l2) k->hs_ps = std::move(set);
+        }
+    // ... on balanced limbs (hensel_ps_bal.hpp): K limbs of lb bits hold the prime itself with four bits to spare (the entry
+    // sums up to four chunk products: below 5 p).  A third set beside hs / hs_ps, which the wavefront-wide forms keep reading
+    if (k->hs_ps)
+      for (int K = 1; K <= 64 && !k->hs_psb; ++K)
+        if (pgpu::hensel_psb_has(K, pgpu::kLimbBits) && bits <= pgpu::kLimbBits * K - 4 && pgpu::hensel_ps_has(k->hs_ps->K, k->hs_ps->lb) &&
+            k->hs_ps->K > K) {
+          std::unique_ptr<pgpu_privkey::HenselSet> set(new pgpu_privkey::HenselSet);
+          RC_TRY(build_hensel_set(k, set.get(), 1, K, p, q, hp, hq, pgpu::kLimbBits, true));
+          if (set->H && set->pair_l2 == k->hs_ps->pair_l2) k->hs_psb = std::move(set);
         }
   }
   return PGPU_OK;

@@ -24,6 +24,9 @@
 //
 // The price is the launch size: 64 exponentiations per wavefront -- 8192 ciphertexts are 256 wavefronts, a quarter of the
 // chip's SIMDs (capi.cpp picks the form for launches that cover the chip alone or together with their neighbour lanes).
+// The 2048-bit class runs hensel_decrypt_psb_kernel<36, 29> of hensel_ps_bal.hpp by default (balanced limbs: 6 % fewer
+// instructions per exponentiation); this kernel's <38, 28> builds remain for PGPU_PS_BALANCED=0, and the key's unsigned
+// constant set for the wavefront-wide forms.
 // Results bit-identical with every other decrypt form (tests/test_gpu_round5.py).  Reference: the two half-width
 // exponentiations of PrivateKey::decryptCRT, ipcl/pri_key.cpp:114-146.
 #ifndef PAILLIERCRYPTOLIB_AMD_CSRC_HENSEL_PS_HPP_

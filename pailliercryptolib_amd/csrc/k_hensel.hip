@@ -6,6 +6,9 @@
 #if defined(PGPU_PART) && (PGPU_PART == 31 || PGPU_PART == 33 || PGPU_PART == 34)
 #include "hensel_ps.hpp"     // whole exponentiations in one lane by product scanning (2048-bit keys; round 5)
 #endif
+#if defined(PGPU_PART) && PGPU_PART == 52
+#include "hensel_ps_bal.hpp" // ... on balanced limbs: 36 limbs of 29 bits instead of 38 of 28 for the 2048-bit class
+#endif
 #if defined(PGPU_PART) && PGPU_PART == 35
 #include "hensel_wave.hpp"   // one exponentiation per WAVEFRONT, a limb per lane: the latency form of small batches (round 6)
 #endif
@@ -26,7 +29,7 @@
 #endif
 
 #ifndef PGPU_PART
-#error "compile with -DPGPU_PART=0..51 (15 and 30 are retired)"
+#error "compile with -DPGPU_PART=0..52 (15 and 30 are retired)"
 #endif
 
 namespace pgpu {
@@ -307,6 +310,23 @@ bool launch_hensel_ps_part34(int K, int lb, const HenselArgs& a, unsigned blocks
   return false;
 }
 static_assert(ps_table_words<19>(32) == 32 * 2 * ((19 + 3) / 4) * 64 * 4, "launch.hpp: hensel_ps_table_words");
+#elif PGPU_PART == 52
+// 2048-bit class on balanced limbs (hensel_ps_bal.hpp): the launch shape, LDS attribute and whole-CU claim of part 31
+bool launch_hensel_psb_part52(int K, int lb, const HenselArgs& a, unsigned blocks, hipStream_t s, unsigned lds_pad) {
+  if (K == 36 && lb == 29) {
+    constexpr unsigned kStatic = sizeof(uint4) * kWavesPerWG * ((36 + 3) / 4) * kWave;
+    const unsigned dyn = lds_pad > kStatic ? lds_pad - kStatic : 0;
+    const bool once = PGPU_LDS_ATTR_ONCE((hensel_decrypt_psb_kernel<36, 29, 2>), 96 * 1024);   // (first launch: see part 16)
+    const bool once1 = PGPU_LDS_ATTR_ONCE((hensel_decrypt_psb_kernel<36, 29, 1>), 96 * 1024);
+    if (dyn && (!once || !once1)) return false;
+    static const bool w1 = [] { const char* e = getenv("PGPU_PS_W1"); return !e || atoi(e) != 0; }();
+    if (dyn && w1) hipLaunchKernelGGL((hensel_decrypt_psb_kernel<36, 29, 1>), dim3(blocks), dim3(kWGThreads), dyn, s, a);
+    else hipLaunchKernelGGL((hensel_decrypt_psb_kernel<36, 29, 2>), dim3(blocks), dim3(kWGThreads), dyn, s, a);
+    return true;
+  }
+  return false;
+}
+static_assert(ps_table_words<36>(32) == 32 * 2 * ((36 + 3) / 4) * 64 * 4, "launch.hpp: hensel_ps_table_words");
 #elif PGPU_PART == 35
 // the latency form: entry (one lane per exponentiation) -> wave kernel (one wavefront per exponentiation) -> exit; a.table is
 // the pair buffer between them (launch.hpp: hensel_wave_pair_words), the window table is dynamic LDS of the wave kernel

@@ -251,6 +251,13 @@ inline bool launch_hensel_ps(int K, int lb, const HenselArgs& a, unsigned blocks
   return launch_hensel_ps_part31(K, lb, a, blocks, s, lds_pad) || launch_hensel_ps_part33(K, lb, a, blocks, s, lds_pad) ||
          launch_hensel_ps_part34(K, lb, a, blocks, s, lds_pad);
 }
+// ... on balanced (signed) limbs, constants of the key's balanced set (hensel_ps_bal.hpp; k_hensel.hip part 52):
+// (36, 29): primes up to 29 * 36 - 4 = 1040 bits, the 2048-bit class
+inline bool hensel_psb_has(int K, int lb) { return K == 36 && lb == 29; }
+bool launch_hensel_psb_part52(int K, int lb, const HenselArgs& a, unsigned blocks, hipStream_t s, unsigned lds_pad);
+inline bool launch_hensel_psb(int K, int lb, const HenselArgs& a, unsigned blocks, hipStream_t s, unsigned lds_pad = 0) {
+  return launch_hensel_psb_part52(K, lb, a, blocks, s, lds_pad);
+}
 // the latency form on the same constants (hensel_wave.hpp; k_hensel.hip part 35): one exponentiation per wavefront, a limb per
 // lane, between the one-lane entry and exit of the kernel above; a.table = the pair buffer, 2K 32-bit words per exponentiation
 inline bool hensel_wave_has(int K, int lb) { return (K == 38 && lb == 28) || (K == 56 && lb == 28) || (K == 19 && lb == 29); }

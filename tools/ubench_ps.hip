@@ -4,14 +4,15 @@
 // (tick = one shader cycle, MI355X_MICROARCH.md), so that cycles per instruction and the clock the chip held are two separate
 // numbers:   cycles/instr = s_memtime span / instructions of the loop;   clock = s_memtime span / wall time of the launch.
 // Round 5's version printed "cycles at 2.4 GHz" computed from WALL time, which cannot tell cadence from clock.
-// Instructions per window: counted by tools/asm_stats.py on this file's code object and passed as argv[1] (default below).
-// build: python tools/build_ubench.py ubench_ps [-DPGPU_PS_SPLIT=1]   (the library's compile step, alignment pass included)
+// Instructions per window: counted by tools/count_loop_instr.py on this file's code object and passed as argv[1] / argv[2]
+// (unsigned form, two- / one-wavefront build) and argv[3] / argv[4] (balanced form); defaults below.
+// build: python tools/build_ubench.py ubench_ps -I<repo>/pailliercryptolib_amd/csrc [-DPGPU_PS_SPLIT=1]   (the library's compile step, alignment pass included)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include <algorithm>
-#include "hensel_ps.hpp"
+#include "hensel_ps_bal.hpp"
 using namespace pgpu;
 
 template <int K, int LB, int MINW>
@@ -52,7 +53,46 @@ __global__ __launch_bounds__(256, MINW) void sq_kernel(const uint32_t* in, const
   }
 }
 
+// the same window on BALANCED limbs (csrc/hensel_ps_bal.hpp: K = 36 limbs of 29 bits carry the prime the unsigned form gives
+// 38 limbs of 28): nn holds the balanced limbs of the modulus, n0inv = -n^-1 mod 2^LB
 template <int K, int LB, int MINW>
+__global__ __launch_bounds__(256, MINW) void sq_kernel_bal(const uint32_t* in, const uint32_t* nn, uint32_t* out,
+                                                           unsigned long long* cyc, int iters, uint32_t n0inv_in) {
+  extern __shared__ uint32_t claim[];
+  __shared__ uint4 park_[kWavesPerWG][(K + 3) / 4][kWave];
+  int32_t a[K], b[K], n[K], c[K], d[K];
+  const int lane = threadIdx.x + blockIdx.x * 256;
+  uint4* slot = &park_[threadIdx.x / kWave][0][threadIdx.x % kWave];
+  __builtin_amdgcn_s_setprio(3);
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    a[j] = (int32_t)in[(size_t)lane * 2 * K + j];
+    b[j] = (int32_t)in[(size_t)lane * 2 * K + K + j];
+    n[j] = (int32_t)ps_uniform(nn[j]);
+  }
+  const uint32_t n0inv = ps_uniform(n0inv_in);
+  const unsigned long long t0 = __builtin_readcyclecounter();
+#pragma unroll 1
+  for (int w = 0; w < iters; ++w) {
+#pragma unroll 1
+    for (int i = 0; i < 5; ++i) psb_pairsqr<K, LB>(a, b, n, n0inv);
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      c[j] = (int32_t)(in[(size_t)lane * 2 * K + j] ^ (w & 1));
+      d[j] = (int32_t)(in[(size_t)lane * 2 * K + K + j] ^ (w & 2));
+    }
+    psb_pairmul<K, LB>(a, b, c, d, n, n0inv, slot);
+  }
+  const unsigned long long t1 = __builtin_readcyclecounter();
+  if (threadIdx.x % kWave == 0) cyc[lane / kWave] = t1 - t0;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    out[(size_t)lane * 2 * K + j] = (uint32_t)a[j];
+    out[(size_t)lane * 2 * K + K + j] = (uint32_t)b[j];
+  }
+}
+
+template <int K, int LB, int MINW, bool BAL = false>
 void run(const char* name, int blocks, unsigned lds, int iters, double instr_per_iter) {
   const size_t lanes = (size_t)blocks * 256, waves = lanes / 64;
   std::vector<uint32_t> h(lanes * 2 * K), hn(2 * K);
@@ -60,18 +100,32 @@ void run(const char* name, int blocks, unsigned lds, int iters, double instr_per
   for (auto& v : h) v = ((uint32_t)rand() * 2654435761u) & ((1u << LB) - 1);
   for (auto& v : hn) v = ((uint32_t)rand() * 2654435761u) & ((1u << LB) - 1);
   hn[0] = hn[K] = (1u << LB) - 1;
+  uint32_t n0inv = 0;
+  if (BAL) {   // limbs in [-2^(LB-2), 2^(LB-2)) (the products keep them balanced), an odd modulus and its true n0inv
+    for (auto& v : h) v = (uint32_t)((int32_t)(v >> 1) - (1 << (LB - 2)));
+    for (auto& v : hn) v = (uint32_t)((int32_t)(v >> 1) - (1 << (LB - 2)));
+    hn[0] |= 1u;
+    hn[K - 1] = 1u << (LB - 10);      // (a positive modulus near 2^(LB*K - 9): the 1040-bit case of the class)
+    uint32_t inv = 1;
+    for (int i = 0; i < 5; ++i) inv *= 2u - hn[0] * inv;
+    n0inv = (0u - inv) & ((1u << LB) - 1);
+  }
   uint32_t *din, *dn, *dout;
   unsigned long long* dcyc;
   hipMalloc(&din, h.size() * 4); hipMalloc(&dn, hn.size() * 4); hipMalloc(&dout, h.size() * 4); hipMalloc(&dcyc, waves * 8);
   hipMemcpy(din, h.data(), h.size() * 4, hipMemcpyHostToDevice);
   hipMemcpy(dn, hn.data(), hn.size() * 4, hipMemcpyHostToDevice);
-  if (lds) hipFuncSetAttribute((const void*)sq_kernel<K, LB, MINW>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+  const void* kfn;
+  if constexpr (BAL) kfn = (const void*)sq_kernel_bal<K, LB, MINW>;
+  else kfn = (const void*)sq_kernel<K, LB, MINW>;
+  if (lds) hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
   hipEvent_t e0, e1;
   hipEventCreate(&e0); hipEventCreate(&e1);
   std::vector<unsigned long long> cyc(waves);
   for (int rep = 0; rep < 4; ++rep) {
     hipEventRecord(e0);
-    hipLaunchKernelGGL((sq_kernel<K, LB, MINW>), dim3(blocks), dim3(256), lds, 0, din, dn, dout, dcyc, iters, 0);
+    if constexpr (BAL) hipLaunchKernelGGL((sq_kernel_bal<K, LB, MINW>), dim3(blocks), dim3(256), lds, 0, din, dn, dout, dcyc, iters, n0inv);
+    else hipLaunchKernelGGL((sq_kernel<K, LB, MINW>), dim3(blocks), dim3(256), lds, 0, din, dn, dout, dcyc, iters, 0);
     hipEventRecord(e1);
     hipEventSynchronize(e1);
     float ms = 0;
@@ -82,7 +136,7 @@ void run(const char* name, int blocks, unsigned lds, int iters, double instr_per
     for (auto v : cyc) mean += (double)v;
     mean /= waves;
     const double instr = iters * instr_per_iter;
-    if (rep) printf("%-46s K=%d blocks=%4d  wall %7.3f ms | s_memtime span per wave: mean %.4g (min %.4g max %.4g) cycles "
+    if (rep) printf("%-56s K=%d blocks=%4d  wall %7.3f ms | s_memtime span per wave: mean %.4g (min %.4g max %.4g) cycles "
                     "= %.3f cycles/instr | clock held %.3f GHz | wall-time figure %.2f ns/instr\n",
                     name, K, blocks, ms, mean, (double)cyc.front(), (double)cyc.back(), mean / instr, (double)cyc.back() / (ms * 1e6),
                     ms * 1e6 / instr);
@@ -101,5 +155,15 @@ int main(int argc, char** argv) {
   run<38, 28, 2>("full chip, one wavefront per SIMD (MINW=2)", 256, 84000, 205, ipi38);
   run<38, 28, 2>("full chip, two wavefronts per SIMD (MINW=2)", 512, 0, 205, ipi38);
   run<38, 28, 1>("one WG only (4 waves on one CU, MINW=1)", 1, 84000, 205, ipi38w1);
+  // the balanced K = 36, LB = 29 window: instructions per window of sq_kernel_bal<36,29,2> / <36,29,1> as argv[3] / argv[4]
+  const double ipi36 = argc > 3 ? atof(argv[3]) : 5 * 5250.0 + 7400.0;
+  const double ipi36w1 = argc > 4 ? atof(argv[4]) : ipi36;
+  printf("# balanced K=36 LB=29  instructions per window: %.0f (two wavefronts per SIMD build) / %.0f (one wavefront per SIMD build)\n",
+         ipi36, ipi36w1);
+  run<36, 29, 1, true>("balanced: lone quarter chip (64 WGs, CU claim, MINW=1)", 64, 84000, 205, ipi36w1);
+  run<36, 29, 1, true>("balanced: full chip, one wavefront per SIMD (MINW=1)", 256, 84000, 205, ipi36w1);
+  run<36, 29, 2, true>("balanced: full chip, one wavefront per SIMD (MINW=2)", 256, 84000, 205, ipi36);
+  run<36, 29, 2, true>("balanced: full chip, two wavefronts per SIMD (MINW=2)", 512, 0, 205, ipi36);
+  run<38, 28, 1>("unsigned again: lone quarter chip (MINW=1)", 64, 84000, 205, ipi38w1);
   return 0;
 }
