@@ -1837,7 +1837,7 @@ int decrypt_on(rt::Device& d, const pgpu_privkey* key, const uint64_t* d_c, uint
       h.window = key->sched[0].w;
       entries = (size_t)1 << (h.window - 1);
     } else {
-      h.window = g_ct_gather.load() ? std::min(masked_decrypt_window(), pick_window(h.exp_bits)) : policy::pick_decrypt_window(h.exp_bits, 2 * count * (size_t)2 * L2 * sizeof(uint32_t));
+      h.window = g_ct_gather.load() ? std::min(masked_decrypt_window(), pick_window(h.exp_bits)) : policy::pick_decrypt_window(h.exp_bits, 2 * count * (size_t)2 * L2 * sizeof(uint32_t), psf && !wavef);
       if (wavef) h.window = std::min(h.window, 5);      // (its table is LDS: 32 entries per wavefront at most)
       entries = (size_t)1 << h.window;
     }
@@ -2439,6 +2439,12 @@ int pgpu_debug_get_wave_decrypt(void) { return pgpu::policy::wave_policy(); }
 int pgpu_debug_get_ps_decrypt(void) { return pgpu::policy::ps_policy(); }
 // tests / A-B measurements: the one-lane form on balanced limbs (hensel_ps_bal.hpp) 1, on the unsigned set 0; returns what was set
 int pgpu_debug_set_ps_balanced(int on) { return g_ps_balanced.exchange(on != 0 ? 1 : 0); }
+// tests / A-B measurements: PGPU_FIXED_WINDOW from inside the process (1..6 forces, 0: by the rules); returns what was set
+int pgpu_debug_set_fixed_window(int w) { return pgpu::policy::set_fixed_window(w); }
+// ... and the window a CRT decrypt of that exponent length and table entry size takes (one_lane: the one-lane forms)
+int pgpu_debug_decrypt_window(int exp_bits, size_t entry_bytes, int one_lane) {
+  return pgpu::policy::pick_decrypt_window(exp_bits, entry_bytes, one_lane != 0);
+}
 // tests / A-B measurements: from how many active neighbour lanes on threads on round-robin lanes take the adaptive forms (0 never)
 int pgpu_debug_set_rr_adapt(int min_busy) { return pgpu::policy::set_rr_adapt(min_busy); }
 

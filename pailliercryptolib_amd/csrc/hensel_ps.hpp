@@ -509,7 +509,11 @@ __global__ __launch_bounds__(kWGThreads, MINW) void hensel_decrypt_ps_kernel(Hen
 
   // ---- c*R as a pair from the pair row of the n^2 domain (hensel_decrypt_kernel: the ct_pair entry) ----
   ps_entry_from_pair_row<K, LB>(A, side, elem, n, n1p, slot, a, b, ma, mb);
-  // ---- window table: entry 0 = one, entry 1 = base, entry e = entry e-1 times base ----
+  // ---- window table, HALF-SQUARED: entry 0 = one, entry 1 = base, entry 2k = (entry k)^2, entry 2k+1 = entry 2k times base
+  // -- 2^(w-1) - 1 pair squarings and as many pair products instead of 2^w - 2 products; a squaring costs 0.71-0.72 of a
+  // product, which also moves the best width for 1024-bit exponents from 5 to 6 bits (policy.cpp: pick_decrypt_window).  The
+  // sequence is the same for every key.  The square of the base sums what base times base summed in the chained table (2ab
+  // for ad + bc), so the bounds of that product hold for it ----
   ps_table_store<K>(tw, 1, a, b);
   {
     uint32_t oa[K], ob[K];
@@ -523,10 +527,14 @@ __global__ __launch_bounds__(kWGThreads, MINW) void hensel_decrypt_ps_kernel(Hen
   // (the base comes back from entry 1 for every product, like the entries of the main loop: held in registers across
   // the loop it cost 92 scratch accesses per product)
 #pragma unroll 1
-  for (int e = 2; e < tsize; ++e) {
+  for (int k = 1; 2 * k < tsize; ++k) {
+    ps_table_load<K>(a, b, tw, k, tsize, false);
+    ps_pairsqr<K, LB>(a, b, n, n1p);
+    ps_table_store<K>(tw, 2 * k, a, b);
+    __builtin_amdgcn_sched_barrier(0);      // (the base is fetched AFTER the squaring: held across it, it costs 2K registers)
     ps_table_load<K>(ma, mb, tw, 1, tsize, false);
     ps_pairmul<K, LB, true>(a, b, ma, mb, n, n1p, 0, slot);
-    ps_table_store<K>(tw, e, a, b);
+    ps_table_store<K>(tw, 2 * k + 1, a, b);
   }
   // ---- main loop: w squarings, one multiplication by a table entry (always, also entry 0 = one) ----
   int win = nwin - 2;

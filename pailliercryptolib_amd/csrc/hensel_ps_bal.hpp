@@ -26,6 +26,14 @@
 
 #include "hensel_ps.hpp"
 
+// 1 (default): a pair squaring forms a2 = 2a once (K shifts) and uses it twice -- the symmetric product takes a2[i] * a[j]
+// (i < j) straight into the column accumulator, with no cross sum of its own and no 64-bit shift-and-add per column, and the
+// second product is a2 * b instead of a * (2b).  0: the cross sums doubled by a shift, b doubled (A/B: tools/ubench_ps.hip has
+// both forms as template arguments; profiles/ps_window6.txt).  Model and column bounds: tests/test_ps_window6_model.py.
+#ifndef PGPU_PSB_DOUBLED
+#define PGPU_PSB_DOUBLED 1
+#endif
+
 namespace pgpu {
 
 // the low LB bits of v as a signed number (v_bfe_i32)
@@ -51,11 +59,14 @@ struct PsbFits {
 //   r = (x1*y1 [+ x2*y2] [+ qio as a number]) * R^-1 mod n,   |limb| <= 2^(LB-1) in, limbs in [-2^(LB-1), 2^(LB-1)) out
 // n: the balanced limbs of the modulus itself (wave-uniform), n0inv = -n^-1 mod 2^LB.  The caller sees to it that the result
 // fits K balanced limbs (then the carry out of the top column is zero).  r may be x2 or y1.
-template <int K, int LB, int NP, bool SYM, int QMODE>
+// DBL (with SYM): x1 holds 2 * y1, |limb| <= 2^LB.  The pairs i < j are x1[i] * y1[j], the diagonal y1[i]^2, all on the one
+// accumulator: a column is at most 18 products of 2^(2LB-1), one square and K q*n terms -- 73 * 2^56 at K = 36, LB = 29.
+template <int K, int LB, int NP, bool SYM, int QMODE, bool DBL = false>
 __device__ __forceinline__ void psb_montmul(int32_t (&r)[K], const int32_t (&x1)[K], const int32_t (&y1)[K],
                                             const int32_t (&x2)[K], const int32_t (&y2)[K], const int32_t (&n)[K],
                                             uint32_t n0inv, int32_t (&qio)[K]) {
   static_assert(!(SYM && NP != 1), "a symmetric product is a single one");
+  static_assert(SYM || !DBL, "the doubled operand belongs to the symmetric product");
   static_assert(PsbFits<K, LB>::value, "a column sums up to 3K products below 2^(2(LB-1)): must stay below 2^63");
   int32_t q[K];
   int64_t acc = 0;
@@ -79,15 +90,25 @@ __device__ __forceinline__ void psb_montmul(int32_t (&r)[K], const int32_t (&x1)
     if constexpr (SYM) {
       constexpr int ilo = col < K ? 0 : col - K + 1;       // pairs i < j, i + j = col, j < K
       constexpr int ihi = (col + 1) / 2;                   // i < col - i
-      if constexpr (ihi > ilo) {
-        int64_t cross = 0;
-        ps_static_for<ihi - ilo>([&](auto ic) __attribute__((always_inline)) {
-          constexpr int i = ilo + decltype(ic)::value;
-          psb_mac(cross, x1[i], x1[col - i]);
-        });
-        acc = (int64_t)((uint64_t)acc + ((uint64_t)cross << 1));
+      if constexpr (DBL) {
+        if constexpr (ihi > ilo) {
+          ps_static_for<ihi - ilo>([&](auto ic) __attribute__((always_inline)) {
+            constexpr int i = ilo + decltype(ic)::value;
+            psb_mac(acc, x1[i], y1[col - i]);
+          });
+        }
+        if constexpr (col % 2 == 0) psb_mac(acc, y1[col / 2], y1[col / 2]);
+      } else {
+        if constexpr (ihi > ilo) {
+          int64_t cross = 0;
+          ps_static_for<ihi - ilo>([&](auto ic) __attribute__((always_inline)) {
+            constexpr int i = ilo + decltype(ic)::value;
+            psb_mac(cross, x1[i], x1[col - i]);
+          });
+          acc = (int64_t)((uint64_t)acc + ((uint64_t)cross << 1));
+        }
+        if constexpr (col % 2 == 0) psb_mac(acc, x1[col / 2], x1[col / 2]);
       }
-      if constexpr (col % 2 == 0) psb_mac(acc, x1[col / 2], x1[col / 2]);
     } else {
       constexpr int ilo = col < K ? 0 : col - K + 1;
       constexpr int ihi = col < K ? col + 1 : K;
@@ -122,13 +143,23 @@ template <int K>
 __device__ __forceinline__ const uint32_t (&psb_bits(const int32_t (&v)[K]))[K] { return reinterpret_cast<const uint32_t(&)[K]>(v); }
 
 // (a, b) = (a, b)^2 (ps_pairsqr):  t = a*a with its digits q;  b = (2*a*b + q) reduced;  a = t.   |2b| <= 2^LB fits int32_t
-template <int K, int LB>
+// DBL: a2 = 2a serves both products (|2a| <= 2^LB as well): t = sym(a2, a), b = (a2*b + q) reduced -- the same column sums in
+// another order of summation, so the same digits and the same limbs, bit for bit.
+template <int K, int LB, bool DBL = (PGPU_PSB_DOUBLED != 0)>
 __device__ __forceinline__ void psb_pairsqr(int32_t (&a)[K], int32_t (&b)[K], const int32_t (&n)[K], uint32_t n0inv) {
   int32_t qd[K], t[K];
-  psb_montmul<K, LB, 1, true, 1>(t, a, a, a, a, n, n0inv, qd);
+  if constexpr (DBL) {
+    int32_t a2[K];
 #pragma unroll
-  for (int j = 0; j < K; ++j) b[j] *= 2;
-  psb_montmul<K, LB, 1, false, 2>(b, a, b, a, b, n, n0inv, qd);
+    for (int j = 0; j < K; ++j) a2[j] = a[j] * 2;
+    psb_montmul<K, LB, 1, true, 1, true>(t, a2, a, a2, a, n, n0inv, qd);
+    psb_montmul<K, LB, 1, false, 2>(b, a2, b, a2, b, n, n0inv, qd);
+  } else {
+    psb_montmul<K, LB, 1, true, 1>(t, a, a, a, a, n, n0inv, qd);
+#pragma unroll
+    for (int j = 0; j < K; ++j) b[j] *= 2;
+    psb_montmul<K, LB, 1, false, 2>(b, a, b, a, b, n, n0inv, qd);
+  }
 #pragma unroll
   for (int j = 0; j < K; ++j) a[j] = t[j];
 }
@@ -327,7 +358,8 @@ __global__ __launch_bounds__(kWGThreads, MINW) void hensel_decrypt_psb_kernel(He
 
   // ---- c*R as a pair from the pair row of the n^2 domain ----
   psb_entry_from_pair_row<K, LB>(A, side, elem, n, n0inv, slot, a, b, ma, mb);
-  // ---- window table: entry 0 = one, entry 1 = base, entry e = entry e-1 times base ----
+  // ---- window table (half-squared, hensel_ps.hpp): entry 0 = one, entry 1 = base, entry 2k = (entry k)^2, entry 2k+1 =
+  // entry 2k times base.  The base leaves the entry below 2.1 p / 4.2 p, like the first product of a chained table ----
   ps_table_store<K>(tw, 1, psb_bits<K>(a), psb_bits<K>(b));
   {
     uint32_t oa[K], ob[K];
@@ -339,10 +371,14 @@ __global__ __launch_bounds__(kWGThreads, MINW) void hensel_decrypt_psb_kernel(He
     ps_table_store<K>(tw, 0, oa, ob);
   }
 #pragma unroll 1
-  for (int e = 2; e < tsize; ++e) {
+  for (int k = 1; 2 * k < tsize; ++k) {
+    ps_table_load<K>(psb_bits<K>(a), psb_bits<K>(b), tw, k, tsize, false);
+    psb_pairsqr<K, LB>(a, b, n, n0inv);
+    ps_table_store<K>(tw, 2 * k, psb_bits<K>(a), psb_bits<K>(b));
+    __builtin_amdgcn_sched_barrier(0);      // (the base is fetched AFTER the squaring: held across it, it costs 2K registers)
     ps_table_load<K>(psb_bits<K>(ma), psb_bits<K>(mb), tw, 1, tsize, false);
     psb_pairmul<K, LB>(a, b, ma, mb, n, n0inv, slot);
-    ps_table_store<K>(tw, e, psb_bits<K>(a), psb_bits<K>(b));
+    ps_table_store<K>(tw, 2 * k + 1, psb_bits<K>(a), psb_bits<K>(b));
   }
   // ---- main loop: w squarings, one multiplication by a table entry (always, also entry 0 = one) ----
   int win = nwin - 2;

@@ -144,10 +144,13 @@ bool pair_mul_seq_pays(int H, int K, size_t count) {
   return pol == 2 || (pol == 1 && waves >= (H >= 8 ? 2 : 1) * kSimds);   // (8-lane groups: see fb_encrypt_seq_pays)
 }
 
+// PGPU_FIXED_WINDOW=w: A/B measurements of the window width (what an LDS-resident table, which
+// holds 8 entries per exponentiation at most, would have to beat); set_fixed_window: the same from a test, 0 = by the rules
+static std::atomic<int> g_fixed_window{env_int("PGPU_FIXED_WINDOW", 0, 1, 6)};
+int set_fixed_window(int w) { return g_fixed_window.exchange(w <= 0 ? 0 : std::min(w, 6)); }
+
 int pick_window(int exp_bits) {
-  // PGPU_FIXED_WINDOW=w: A/B measurements of the window width (what an LDS-resident table, which
-  // holds 8 entries per exponentiation at most, would have to beat)
-  static const int forced = env_int("PGPU_FIXED_WINDOW", 0, 1, 6);
+  const int forced = g_fixed_window.load();
   if (forced) return forced;
   int best = 1;
   long best_cost = 1L << 60;
@@ -164,11 +167,33 @@ int pick_window(int exp_bits) {
 // The window table of a launch is `entry_bytes` (all exponentiations of the launch, one entry each) x 2^w: w = 6 only while
 // that stays under kDecryptTableCap -- a 65536-ciphertext launch of a 3072-bit key is 3.8 GB at w = 6 (config 4: kept), a
 // 1 M-ciphertext one would be 60 GB for a gain of 1.2 %; entry_bytes = 0: no cap (the by-exponent rule alone).
+//
+// The ONE-LANE forms (hensel_ps.hpp, hensel_ps_bal.hpp) build a half-squared table -- entry 2k = (entry k)^2, entry 2k+1 =
+// entry 2k (x) base: 2^(w-1) - 1 pair squarings and as many pair products -- and load the top digit's entry directly, so an
+// exponentiation is (nwin - 1) w + 2^(w-1) - 1 squarings and (nwin - 1) + 2^(w-1) - 1 products, and a squaring is the cheaper
+// of the two: the width is the one of the least WEIGHTED count, the weights being the instructions of the two loops of
+// hensel_decrypt_psb_kernel<36,29,1> (profiles/ps_balanced.txt; the unsigned kernels have the same ratio within 2 %:
+// 5556 / 7844).  1024-bit exponents: 1035 + 219 at w = 5, 1051 + 201 at w = 6 -- 7.04 M against 6.99 M instructions; 512
+// bits stay at 5 (3.61 M against 3.69 M), 1536 bits at 6.  The same cap holds: 8192 ciphertexts of a 2048-bit key are 302 MB at
+// w = 6.  The multi-lane forms (sequential-halves, paired, wavefront-wide) build their tables with chained products in kernels
+// of their own and keep the rule above.
 constexpr size_t kDecryptTableCap = (size_t)4 << 30;
-int pick_decrypt_window(int exp_bits, size_t entry_bytes) {
+constexpr long kPsSqrInstr = 5260, kPsMulInstr = 7278;
+int pick_decrypt_window(int exp_bits, size_t entry_bytes, bool one_lane) {
   const int w5 = pick_window(exp_bits);
-  static const int forced = env_int("PGPU_FIXED_WINDOW", 0, 1, 6);
-  if (forced || exp_bits < 1280) return w5;
+  if (g_fixed_window.load()) return w5;
+  if (one_lane) {
+    int best = 1;
+    long best_cost = 1L << 60;
+    for (int w = 1; w <= 6; ++w) {
+      if (w == 6 && entry_bytes > (kDecryptTableCap >> 6)) break;   // (the cap is on the sixth bit, as below)
+      const long nwin = (exp_bits + w - 1) / w, build = (1L << (w - 1)) - 1;
+      const long cost = ((nwin - 1) * w + build) * kPsSqrInstr + ((nwin - 1) + build) * kPsMulInstr;
+      if (cost < best_cost) { best_cost = cost; best = w; }
+    }
+    return best;
+  }
+  if (exp_bits < 1280) return w5;
   if (entry_bytes > (kDecryptTableCap >> 6)) return w5;
   const long c5 = ((1L << w5) - 2) + (exp_bits + w5 - 1) / w5, c6 = ((1L << 6) - 2) + (exp_bits + 5) / 6;
   return c6 < c5 ? 6 : w5;

@@ -76,7 +76,11 @@ bool pair_mul_seq_pays(int H, int K, size_t count);
 int pick_window(int exp_bits);
 // ... of the CRT-decrypt exponentiation (a secret exponent shared by the launch): w = 6 as well from 1280 bits up
 // (entry_bytes: one table entry of every exponentiation of the launch; w = 6 only while the whole table stays under 4 GiB)
-int pick_decrypt_window(int exp_bits, size_t entry_bytes = 0);
+// one_lane: the launch runs a one-lane form (hensel_ps.hpp / hensel_ps_bal.hpp: half-squared table) -- the w in 1..6 of the
+// least count weighted by the instructions of a pair squaring and a pair product: 6 from 1024-bit exponents up, same cap
+int pick_decrypt_window(int exp_bits, size_t entry_bytes = 0, bool one_lane = false);
+// PGPU_FIXED_WINDOW from inside the process (tests): w in 1..6 forces, 0 gives the rules back; returns what was set before
+int set_fixed_window(int w);
 // ... under the masked table gather (every entry of the table read at every window product: small on purpose)
 int masked_decrypt_window();
 

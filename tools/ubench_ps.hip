@@ -6,6 +6,11 @@
 // Round 5's version printed "cycles at 2.4 GHz" computed from WALL time, which cannot tell cadence from clock.
 // Instructions per window: counted by tools/count_loop_instr.py on this file's code object and passed as argv[1] / argv[2]
 // (unsigned form, two- / one-wavefront build) and argv[3] / argv[4] (balanced form); defaults below.
+// Third part (the 6-bit window and the doubled operand of the balanced pair squaring): exp_kernel_bal runs the operation sequence
+// of ONE whole exponentiation -- table build, then nwin - 1 windows of w squarings + 1 product -- in four forms from this one
+// binary: the parent's (30 chained products, 204 x (5 + 1)), the half-squared table at w = 5 (15 x (1 + 1), 204 x (5 + 1)) and at
+// w = 6 (31 x (1 + 1), 170 x (6 + 1)), each with psb_pairsqr<K, LB, false> and <K, LB, true>; and 1020 squarings alone in both.
+// Reported in shader cycles per exponentiation (no instruction count needed).
 // build: python tools/build_ubench.py ubench_ps -I<repo>/pailliercryptolib_amd/csrc [-DPGPU_PS_SPLIT=1]   (the library's compile step, alignment pass included)
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -92,6 +97,99 @@ __global__ __launch_bounds__(256, MINW) void sq_kernel_bal(const uint32_t* in, c
   }
 }
 
+// one exponentiation's operations on balanced limbs: `build` times ([a squaring if half] + a product), then `nwin` times
+// (w squarings + [a product if do_mul]); DBL: the pair squaring on the doubled operand
+template <int K, int LB, int MINW, bool DBL>
+__global__ __launch_bounds__(256, MINW) void exp_kernel_bal(const uint32_t* in, const uint32_t* nn, uint32_t* out,
+                                                            unsigned long long* cyc, uint32_t n0inv_in, int build, int half,
+                                                            int nwin, int w, int do_mul) {
+  extern __shared__ uint32_t claim[];
+  __shared__ uint4 park_[kWavesPerWG][(K + 3) / 4][kWave];
+  int32_t a[K], b[K], n[K], c[K], d[K];
+  const int lane = threadIdx.x + blockIdx.x * 256;
+  uint4* slot = &park_[threadIdx.x / kWave][0][threadIdx.x % kWave];
+  __builtin_amdgcn_s_setprio(3);
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    a[j] = (int32_t)in[(size_t)lane * 2 * K + j];
+    b[j] = (int32_t)in[(size_t)lane * 2 * K + K + j];
+    n[j] = (int32_t)ps_uniform(nn[j]);
+  }
+  const uint32_t n0inv = ps_uniform(n0inv_in);
+  const unsigned long long t0 = __builtin_readcyclecounter();
+#pragma unroll 1
+  for (int e = 0; e < build; ++e) {
+    if (half) psb_pairsqr<K, LB, DBL>(a, b, n, n0inv);
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      c[j] = (int32_t)(in[(size_t)lane * 2 * K + j] ^ (e & 1));
+      d[j] = (int32_t)(in[(size_t)lane * 2 * K + K + j] ^ (e & 2));
+    }
+    psb_pairmul<K, LB>(a, b, c, d, n, n0inv, slot);
+  }
+#pragma unroll 1
+  for (int wi = 0; wi < nwin; ++wi) {
+#pragma unroll 1
+    for (int i = 0; i < w; ++i) psb_pairsqr<K, LB, DBL>(a, b, n, n0inv);
+    if (do_mul) {
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        c[j] = (int32_t)(in[(size_t)lane * 2 * K + j] ^ (wi & 1));
+        d[j] = (int32_t)(in[(size_t)lane * 2 * K + K + j] ^ (wi & 2));
+      }
+      psb_pairmul<K, LB>(a, b, c, d, n, n0inv, slot);
+    }
+  }
+  const unsigned long long t1 = __builtin_readcyclecounter();
+  if (threadIdx.x % kWave == 0) cyc[lane / kWave] = t1 - t0;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    out[(size_t)lane * 2 * K + j] = (uint32_t)a[j];
+    out[(size_t)lane * 2 * K + K + j] = (uint32_t)b[j];
+  }
+}
+
+template <int K, int LB, bool DBL>
+void run_exp(const char* name, int blocks, unsigned lds, int build, int half, int nwin, int w, int do_mul) {
+  const size_t lanes = (size_t)blocks * 256, waves = lanes / 64;
+  std::vector<uint32_t> h(lanes * 2 * K), hn(K);
+  srand(1);
+  for (auto& v : h) v = (uint32_t)((int32_t)((((uint32_t)rand() * 2654435761u) & ((1u << LB) - 1)) >> 1) - (1 << (LB - 2)));
+  for (auto& v : hn) v = (uint32_t)((int32_t)((((uint32_t)rand() * 2654435761u) & ((1u << LB) - 1)) >> 1) - (1 << (LB - 2)));
+  hn[0] |= 1u;
+  hn[K - 1] = 1u << (LB - 10);
+  uint32_t inv = 1;
+  for (int i = 0; i < 5; ++i) inv *= 2u - hn[0] * inv;
+  const uint32_t n0inv = (0u - inv) & ((1u << LB) - 1);
+  uint32_t *din, *dn, *dout;
+  unsigned long long* dcyc;
+  hipMalloc(&din, h.size() * 4); hipMalloc(&dn, hn.size() * 4); hipMalloc(&dout, h.size() * 4); hipMalloc(&dcyc, waves * 8);
+  hipMemcpy(din, h.data(), h.size() * 4, hipMemcpyHostToDevice);
+  hipMemcpy(dn, hn.data(), hn.size() * 4, hipMemcpyHostToDevice);
+  if (lds) hipFuncSetAttribute((const void*)exp_kernel_bal<K, LB, 1, DBL>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+  hipEvent_t e0, e1;
+  hipEventCreate(&e0); hipEventCreate(&e1);
+  std::vector<unsigned long long> cyc(waves);
+  for (int rep = 0; rep < 4; ++rep) {
+    hipEventRecord(e0);
+    hipLaunchKernelGGL((exp_kernel_bal<K, LB, 1, DBL>), dim3(blocks), dim3(256), lds, 0, din, dn, dout, dcyc, n0inv, build, half, nwin, w, do_mul);
+    hipEventRecord(e1);
+    hipEventSynchronize(e1);
+    float ms = 0;
+    hipEventElapsedTime(&ms, e0, e1);
+    hipMemcpy(cyc.data(), dcyc, waves * 8, hipMemcpyDeviceToHost);
+    std::sort(cyc.begin(), cyc.end());
+    double mean = 0;
+    for (auto v : cyc) mean += (double)v;
+    mean /= waves;
+    const int sq = (half ? build : 0) + nwin * w, mul = build + (do_mul ? nwin : 0);
+    if (rep) printf("%-52s doubled=%d  %4d squarings + %3d products  wall %7.3f ms | cycles per exponentiation: mean %.5g (min %.5g max %.5g)"
+                    " | clock held %.3f GHz\n", name, (int)DBL, sq, mul, ms, mean, (double)cyc.front(), (double)cyc.back(),
+                    (double)cyc.back() / (ms * 1e6));
+  }
+  hipFree(din); hipFree(dn); hipFree(dout); hipFree(dcyc);
+}
+
 template <int K, int LB, int MINW, bool BAL = false>
 void run(const char* name, int blocks, unsigned lds, int iters, double instr_per_iter) {
   const size_t lanes = (size_t)blocks * 256, waves = lanes / 64;
@@ -165,5 +263,17 @@ int main(int argc, char** argv) {
   run<36, 29, 2, true>("balanced: full chip, one wavefront per SIMD (MINW=2)", 256, 84000, 205, ipi36);
   run<36, 29, 2, true>("balanced: full chip, two wavefronts per SIMD (MINW=2)", 512, 0, 205, ipi36);
   run<38, 28, 1>("unsigned again: lone quarter chip (MINW=1)", 64, 84000, 205, ipi38w1);
+  // whole exponentiations of a 1024-bit exponent on balanced limbs, lone quarter chip with the CU claim, MINW = 1:
+  // the parent's form first and last
+  printf("# one exponentiation (1024-bit exponent), balanced K=36 LB=29, lone quarter chip (64 WGs, CU claim, MINW=1)\n");
+  run_exp<36, 29, false>("parent: w=5, chained table (30 products)", 64, 84000, 30, 0, 204, 5, 1);
+  run_exp<36, 29, false>("w=5, half-squared table", 64, 84000, 15, 1, 204, 5, 1);
+  run_exp<36, 29, false>("w=6, half-squared table", 64, 84000, 31, 1, 170, 6, 1);
+  run_exp<36, 29, true>("w=5, chained table (30 products)", 64, 84000, 30, 0, 204, 5, 1);
+  run_exp<36, 29, true>("w=5, half-squared table", 64, 84000, 15, 1, 204, 5, 1);
+  run_exp<36, 29, true>("w=6, half-squared table", 64, 84000, 31, 1, 170, 6, 1);
+  run_exp<36, 29, false>("squarings alone", 64, 84000, 0, 0, 170, 6, 0);
+  run_exp<36, 29, true>("squarings alone", 64, 84000, 0, 0, 170, 6, 0);
+  run_exp<36, 29, false>("parent again: w=5, chained table (30 products)", 64, 84000, 30, 0, 204, 5, 1);
   return 0;
 }
