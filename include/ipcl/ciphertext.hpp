@@ -14,6 +14,8 @@ namespace ipcl {
 class CipherText;
 namespace ext {   // include/ipcl/ext/linear.hpp
 CipherText matVec(const PlainText& w, std::size_t rows, const CipherText& x);
+CipherText sparseMatVec(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx, const PlainText& w,
+                        const CipherText& x);
 // include/ipcl/ext/aggregate.hpp
 CipherText segmentSum(const CipherText& x, const std::vector<uint32_t>& ids, std::size_t n_segments, std::size_t groups);
 CipherText segmentScan(const CipherText& x, std::size_t seg_len, bool reverse);
@@ -46,6 +48,11 @@ class CipherText : public BaseText {
   friend class PublicKey;
   friend CipherText ext::matVec(const PlainText& w, std::size_t rows, const CipherText& x);
   CipherText linearMap(const PlainText& w, std::size_t rows) const;   // prod_j this[j]^w[i][j]: csrc/host/linear.cpp
+  friend CipherText ext::sparseMatVec(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx,
+                                      const PlainText& w, const CipherText& x);
+  // prod_t this[col_idx[t]]^w[t] over the CSR entries t of every row: csrc/host/linear.cpp
+  CipherText sparseLinearMap(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx,
+                             const PlainText& w) const;
   friend CipherText ext::segmentSum(const CipherText& x, const std::vector<uint32_t>& ids, std::size_t n_segments,
                                     std::size_t groups);
   // prod_{j: ids[g][j] == s} this[j]: csrc/host/aggregate.cpp

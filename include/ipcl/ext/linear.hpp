@@ -4,6 +4,14 @@
 //   matVec(w, rows, x)   y[i] = sum_j w[i*cols + j] * x[j]   under the encryption, cols = x.getSize():
 //                        Y[i] = prod_j X[j]^w[i][j] mod n^2 -- an encrypted linear layer, a weighted aggregate
 //   dot(w, x)            the rows = 1 case
+//   sparseMatVec(row_ptr, col_idx, w, x)
+//                        the same map with the plaintext matrix in CSR form, rows = row_ptr.size() - 1:
+//                        Y[i] = prod_{ row_ptr[i] <= t < row_ptr[i+1] } X[col_idx[t]]^w[t] mod n^2 -- a neighbourhood
+//                        aggregation over a graph, a sparse or pruned layer, a convolution as a banded matrix, a weighted
+//                        group-by.  w holds the row_ptr.back() weights in CSR order.  Entries of a row need not be sorted, a
+//                        column named twice contributes twice, an empty row yields an encryption of 0 (the ciphertext 1).
+//                        One pgpu_batch_ct_spmv call: the window tables of the x[j] shared by all rows, the squarings
+//                        shared by the terms of a chain of a row.
 //
 // w: rows*cols non-negative plaintext weights, row-major (negative numbers have no encoding in the reference either; pass
 // w mod n).  One fused launch sequence on the GPU (pgpu_batch_ct_matvec: window tables of the x[j] shared by all rows, the
@@ -15,6 +23,8 @@
 #define PAILLIERCRYPTOLIB_AMD_IPCL_EXT_LINEAR_HPP_
 
 #include <cstddef>
+#include <cstdint>
+#include <vector>
 
 #include "ipcl/ciphertext.hpp"
 #include "ipcl/plaintext.hpp"
@@ -24,6 +34,8 @@ namespace ext {
 
 CipherText matVec(const PlainText& w, std::size_t rows, const CipherText& x);
 CipherText dot(const PlainText& w, const CipherText& x);
+CipherText sparseMatVec(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx, const PlainText& w,
+                        const CipherText& x);
 
 }  // namespace ext
 }  // namespace ipcl

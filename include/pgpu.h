@@ -396,6 +396,41 @@ int pgpu_batch_ct_pack(const pgpu_pubkey* key, const pgpu_batch* x, size_t seg_l
  * PGPU_ERR_INVALID_PARAM: key_bits < 1, rows == 0, seg_len == 0, slot_bits < 1, seg_len * slot_bits > key_bits - 1, a product
  * count beyond size_t.  PGPU_ERR_UNSUPPORTED: no pair rows for keys of key_bits. */
 int pgpu_ct_pack_plan(int key_bits, size_t rows, size_t seg_len, int slot_bits, int* lanes, int* limbs, size_t* products);
+/* Encrypted sparse matrix-vector product (a neighbourhood aggregation over a graph, a sparse or pruned linear layer, a
+ * convolution as a banded matrix, SUM(v*x) GROUP BY id): x a resident ciphertext batch of cols = pgpu_batch_count(x)
+ * elements (pair rows, or uploaded plain ciphertext words: converted on the way in), the plaintext matrix A in CSR form:
+ * row_ptr[rows + 1] and col_idx[nnz] HOST arrays, w a plain uploaded batch of nnz = row_ptr[rows] exponents in CSR order,
+ * each < 2^e_bits (bits at and above e_bits are ignored):
+ *     out[i] = prod_{ row_ptr[i] <= t < row_ptr[i+1] } x[col_idx[t]]^w[t] mod n^2
+ *     i.e. Dec(out[i]) = sum_t w[t] * Dec(x[col_idx[t]]) mod n
+ * The entries of a row need not be sorted by column; a column named twice in a row contributes twice; a zero weight
+ * contributes 1; an empty row yields the ciphertext 1, as an empty segment and an all-zero matvec row do.  Negative
+ * weights have no encoding: pass w mod n.  The window tables of the x[j] are built once and shared by all rows; every row
+ * is cut into chains of at most `chunk` entries, each one multi-exponentiation with its own e_bits squarings, and the
+ * partial products of the rows of several chains are folded level by level ("Encrypted sparse matrix-vector
+ * product").  The result is an ordinary resident ciphertext batch of `rows` elements in pair rows on the lane of x; x is
+ * left unchanged; row_ptr and col_idx may be reused as soon as the call returns.
+ * PGPU_ERR_INVALID_PARAM: null / stale handles, rows == 0, row_ptr[0] != 0, row_ptr not non-decreasing, nnz == 0,
+ * count(w) != nnz, w not a plain uploaded batch, a col_idx[t] >= cols, e_bits < 1 or wider than the rows of w, ciphertext
+ * width mismatch, a batch of another key, rows, nnz or the number of chains beyond what 32-bit descriptors address (2^31).
+ * PGPU_ERR_UNSUPPORTED: keys without pair rows (beyond 3072 bits; PGPU_PAIR_ROWS=0 / PGPU_HENSEL=0), pools of more than one
+ * GPU, and -- SIDE CHANNELS -- the masked table-gather policy: the tables are indexed by the caller's PLAINTEXT column
+ * numbers and by digits of the PLAINTEXT weights w (never by key material or by anything encrypted), which is the indexed
+ * access of the default policy; with pgpu_set_table_gather_policy(1) the call is refused rather than run with an access
+ * pattern the policy excludes.
+ * All refusals are decided on the host before any launch and leave *out untouched. */
+int pgpu_batch_ct_spmv(const pgpu_pubkey* key, const pgpu_batch* x, const uint64_t* row_ptr, const uint32_t* col_idx,
+                       const pgpu_batch* w, size_t rows, int e_bits, pgpu_batch** out);
+/* What a call of this shape would run (host-side query, needs no device).  window: the window width (1..6); chunk: the
+ * entries one chain multiplies in per window; levels: 1 (the multi-exponentiation) plus the fold launches that the longest
+ * row needs (the table build is one launch more); table_bytes: cols * 2^window pair rows -- the table covers EVERY column
+ * of x; products: the pair products of the call, table included, counting the longest row cut by the chunk and the
+ * other rows as equally long (exact while longest_row <= chunk and for rows of one length, an estimate otherwise).  The rule is policy.hpp: spmv_*;
+ * PGPU_SPMV_WINDOW / PGPU_SPMV_CHUNK (c >= 1) force the two values, read at every call.
+ * PGPU_ERR_INVALID_PARAM: key_bits < 1, rows == 0, cols == 0, nnz == 0, longest_row == 0 or > nnz, nnz > rows * longest_row,
+ * e_bits < 1, rows or nnz of 2^31 or more.  PGPU_ERR_UNSUPPORTED: no pair rows for keys of key_bits. */
+int pgpu_ct_spmv_plan(int key_bits, size_t rows, size_t cols, size_t nnz, size_t longest_row, int e_bits,
+                      int* window, int* chunk, int* levels, size_t* table_bytes, size_t* products);
 
 /* ---- instrumentation used by bench.py (roofline) ----
  * With timing enabled every kernel launch is bracketed by two HIP events recorded on the stream
@@ -410,7 +445,8 @@ typedef enum pgpu_kernel_kind {
   PGPU_KERNEL_MATVEC = 5,     /* every launch of pgpu_batch_ct_matvec: table build, multi-exponentiation, fold */
   PGPU_KERNEL_SEGSUM = 6,     /* every launch of pgpu_batch_ct_segment_sum: one per level */
   PGPU_KERNEL_SEGSCAN = 7,    /* every launch of pgpu_batch_ct_segment_scan: up-sweeps (segsum_kernel) and scans */
-  PGPU_KERNEL_PACK = 8        /* the launch of pgpu_batch_ct_pack */
+  PGPU_KERNEL_PACK = 8,       /* the launch of pgpu_batch_ct_pack */
+  PGPU_KERNEL_SPMV = 9        /* every launch of pgpu_batch_ct_spmv: table build, multi-exponentiation, fold levels */
 } pgpu_kernel_kind;
 int pgpu_set_timing(int enabled);
 int pgpu_timing_collect(int* kinds, double* ms, int max_entries);

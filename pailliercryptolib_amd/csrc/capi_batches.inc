@@ -805,6 +805,190 @@ int pgpu_batch_ct_segment_sum(const pgpu_pubkey* key, const pgpu_batch* x, const
   return PGPU_OK;
 }
 
+// ---- encrypted sparse matrix-vector product (hensel_spmv.hpp; policy.hpp: spmv_*) ----
+int pgpu_ct_spmv_plan(int key_bits, size_t rows, size_t cols, size_t nnz, size_t longest_row, int e_bits,
+                      int* window, int* chunk, int* levels, size_t* table_bytes, size_t* products) {
+  constexpr size_t kMax = (size_t)1 << 31;
+  if (key_bits < 1 || rows == 0 || cols == 0 || nnz == 0 || e_bits < 1 || longest_row == 0 || longest_row > nnz ||
+      rows >= kMax || nnz >= kMax || (nnz + longest_row - 1) / longest_row > rows)
+    return fail(PGPU_ERR_INVALID_PARAM, "spmv plan: key_bits, rows, cols, nnz and e_bits must be positive, rows and nnz below 2^31, "
+                                        "longest_row between ceil(nnz / rows) and nnz");
+  int G = 0, K = 0;
+  if (!policy::matvec_geometry(key_bits, &G, &K))
+    return fail(PGPU_ERR_UNSUPPORTED, "spmv: keys of this size have no pair rows (1024- to 3072-bit key classes only)");
+  const size_t row_bytes = (size_t)2 * G * K * sizeof(uint32_t);
+  const int c = policy::spmv_chunk(G, nnz, rows);
+  const size_t chains = policy::spmv_chains_estimate(rows, nnz, longest_row, c);
+  const int w = policy::spmv_window(rows, cols, nnz, chains, e_bits, row_bytes);
+  if (window) *window = w;
+  if (chunk) *chunk = c;
+  if (levels) *levels = policy::spmv_levels(c, longest_row);
+  if (table_bytes) *table_bytes = cols * ((size_t)1 << w) * row_bytes;
+  if (products) *products = (size_t)policy::spmv_products(rows, cols, nnz, chains, e_bits, w);
+  return PGPU_OK;
+}
+
+int pgpu_batch_ct_spmv(const pgpu_pubkey* key, const pgpu_batch* x, const uint64_t* row_ptr, const uint32_t* col_idx,
+                       const pgpu_batch* w, size_t rows, int e_bits, pgpu_batch** out) {
+  RC_TRY(rt::check_ready());
+  if (!key || !x || !row_ptr || !col_idx || !w || !out) return fail(PGPU_ERR_INVALID_PARAM, "null argument");
+  RC_TRY(check_gen(key->gen, "key"));
+  RC_TRY(check_gen(x->gen, "batch"));
+  RC_TRY(check_gen(w->gen, "batch"));
+  const int W = 2 * key->n_words;
+  const size_t cols = x->count;
+  // (CSR positions, rows and chains are 31-bit fields of a descriptor)
+  constexpr size_t kMax = (size_t)1 << 31;
+  if (rows == 0 || rows >= kMax) return fail(PGPU_ERR_INVALID_PARAM, "spmv error: rows must be positive and below 2^31");
+  if (x->words != W) return fail(PGPU_ERR_INVALID_PARAM, "spmv error: ciphertext width mismatch");
+  if (w->mont || w->pair_l2) return fail(PGPU_ERR_INVALID_PARAM, "spmv error: the weights must be a plain uploaded batch");
+  if (row_ptr[0] != 0) return fail(PGPU_ERR_INVALID_PARAM, "spmv error: row_ptr[0] must be 0");
+  for (size_t i = 0; i < rows; ++i)
+    if (row_ptr[i + 1] < row_ptr[i]) return fail(PGPU_ERR_INVALID_PARAM, "spmv error: row_ptr must be non-decreasing");
+  if (row_ptr[rows] == 0) return fail(PGPU_ERR_INVALID_PARAM, "spmv error: the matrix has no entries (nnz == 0)");
+  if (row_ptr[rows] >= kMax) return fail(PGPU_ERR_INVALID_PARAM, "spmv error: nnz must stay below 2^31");
+  const size_t nnz = (size_t)row_ptr[rows];
+  if (w->count != nnz) return fail(PGPU_ERR_INVALID_PARAM, "spmv error: Size mismatch! (the weights must hold row_ptr[rows] values)");
+  for (size_t t = 0; t < nnz; ++t)
+    if (col_idx[t] >= cols) return fail(PGPU_ERR_INVALID_PARAM, "spmv error: a column index is not below count(x)");
+  if (e_bits < 1 || e_bits > 64 * w->words) return fail(PGPU_ERR_INVALID_PARAM, "spmv error: e_bits outside the rows of the weight batch");
+  if (!same_domain(x->mont, key->nsq)) return fail(PGPU_ERR_INVALID_PARAM, "spmv error: batch belongs to a different key");
+  if (rt::pool_size() > 1)
+    return fail(PGPU_ERR_UNSUPPORTED, "spmv: pools of more than one GPU are not supported (rows are not sharded yet)");
+  const pgpu_pubkey::PubForm* pf = pair_form(key);
+  if (!pf || !pgpu::spmv_has(pf->H, pf->K))
+    return fail(PGPU_ERR_UNSUPPORTED, "spmv: key has no pair form (1024- to 3072-bit keys; PGPU_PAIR_ROWS=0 / PGPU_HENSEL=0 switch it off)");
+  // the window tables are addressed by the caller's plaintext column numbers and by digits of the caller's plaintext
+  // weights: indexed access.  Under the masked policy the call is refused rather than quietly breaking that promise.
+  if (g_ct_gather.load())
+    return fail(PGPU_ERR_UNSUPPORTED, "spmv: the masked table-gather policy is on (pgpu_set_table_gather_policy / PGPU_CT_GATHER) and "
+                                      "this call indexes its window tables by the plaintext column numbers and by digits of the "
+                                      "plaintext weights; no masked variant exists");
+  if (x->pair_l2 && (x->pair_l2 != pf->H * pf->K || !(x->pair_form->n == key->n)))
+    return fail(PGPU_ERR_INVALID_PARAM, "spmv error: batch belongs to a different key");
+  // the plan, on the host: chain descriptors, then the fold levels over the partial rows
+  const int G = pf->H, K = pf->K, l2 = G * K;
+  const size_t LQ = (size_t)2 * l2, row_bytes = LQ * sizeof(uint32_t);
+  policy::SpmvPlan plan;
+  if (!policy::spmv_plan(row_ptr, rows, policy::spmv_chunk(G, nnz, rows), &plan))
+    return fail(PGPU_ERR_INVALID_PARAM, "spmv error: more chains than a 32-bit descriptor addresses");
+  const int win = policy::spmv_window(rows, cols, nnz, plan.n_chains, e_bits, row_bytes);
+  // one image for the device: the column indices, then the descriptors of the chains and of every fold level
+  const size_t idx_bytes = (nnz * sizeof(uint32_t) + 15) & ~(size_t)15;
+  // partial rows: the chains write region 0, fold level f reads region f & 1 and writes the other one
+  size_t image_bytes = idx_bytes + plan.chains.size() * sizeof(pgpu::SegsumChunk), region[2] = {plan.partial_rows, 0};
+  for (size_t f = 0; f < plan.fold.levels.size(); ++f) {
+    image_bytes += plan.fold.levels[f].chunks.size() * sizeof(pgpu::SegsumChunk);
+    region[(f + 1) & 1] = std::max(region[(f + 1) & 1], plan.fold.levels[f].partial_rows);
+  }
+  std::vector<char> image(image_bytes, 0);
+  std::memcpy(image.data(), col_idx, nnz * sizeof(uint32_t));
+  {
+    size_t at = idx_bytes;
+    std::memcpy(image.data() + at, plan.chains.data(), plan.chains.size() * sizeof(pgpu::SegsumChunk));
+    at += plan.chains.size() * sizeof(pgpu::SegsumChunk);
+    for (const auto& lv : plan.fold.levels) {
+      std::memcpy(image.data() + at, lv.chunks.data(), lv.chunks.size() * sizeof(pgpu::SegsumChunk));
+      at += lv.chunks.size() * sizeof(pgpu::SegsumChunk);
+    }
+  }
+  std::unique_ptr<pgpu_batch> tx;
+  RC_TRY(as_pair_batch(key, x, &x, &tx));
+  std::unique_ptr<pgpu_batch> o;
+  RC_TRY(new_batch(rows, W, &o, l2, x->lane));
+  o->pair_form = pair_form_shared(key);
+  rt::Device& dev = rt::device(0);
+  rt::DeviceGuard g(dev.ordinal);
+  hipStream_t s = dev.bs(x->lane);
+  RC_TRY(lanes_order(w, x->lane, true));
+  // table, plan image and partial rows: the block arena, on the lane's stream like the operands themselves -- what the
+  // arena hands out again it hands to this stream, behind the kernels below
+  rt::DevMem table, dimage, partial;
+  RC_TRY(table.alloc(dev, s, cols * ((size_t)1 << win) * row_bytes));
+  RC_TRY(dimage.alloc(dev, s, image_bytes));
+  if (region[0]) RC_TRY(partial.alloc(dev, s, (region[0] + region[1]) * row_bytes));
+  if (image_bytes <= kBounceBytes) {
+    Bounce& bn = bounce();
+    RC_TRY(bn.ready());
+    std::memcpy(bn.p, image.data(), image_bytes);
+    HIP_TRY(hipMemcpyAsync(dimage.p, bn.p, image_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(bn.ev, s));
+    bn.pending = true;
+  } else {   // through a worker lane's staging buffers, queued on the same stream: nothing is waited for
+    rt::TaskGroup tg;
+    void* dst = dimage.p;
+    const char* src = image.data();
+    tg.run(dev, [=](rt::Lane& lane) -> int { return lane.h2d(dst, src, image_bytes, s); });
+    RC_TRY(tg.wait());
+  }
+  const size_t ipw = 64 / (size_t)G;
+  auto blocks_of = [](size_t waves) { return (unsigned)((waves + pgpu::kWavesPerWG - 1) / pgpu::kWavesPerWG); };
+  {
+    // the unchanged table build of the matvec: T[j][d] = x[j]^d for every column of x
+    pgpu::MatvecArgs ta{};
+    ta.ctx = hensel_pub_view(pf, dev.index);
+    ta.x = x->prow(0);
+    ta.table = (uint32_t*)table.p;
+    ta.window = win;
+    ta.cols = cols;
+    TimerScope t(dev, s, PGPU_KERNEL_SPMV, PGPU_FORM_SEQ);
+    if (!pgpu::launch_matvec_table(G, K, ta, blocks_of((cols + ipw - 1) / ipw), s))
+      return fail(PGPU_ERR_UNSUPPORTED, "spmv kernels not compiled for this key class");
+    HIP_TRY(hipGetLastError());
+    t.stop();
+  }
+  uint32_t* const reg[2] = {(uint32_t*)partial.p, partial.p ? (uint32_t*)partial.p + region[0] * LQ : nullptr};
+  size_t at = idx_bytes;
+  {
+    pgpu::SpmvArgs a{};
+    a.ctx = hensel_pub_view(pf, dev.index);
+    a.table = (const uint32_t*)table.p;
+    a.col_idx = (const uint32_t*)dimage.p;
+    a.w = w->ptr(0);
+    a.w_stride = (size_t)w->words;
+    a.w_words = w->words;
+    a.e_bits = e_bits;
+    a.window = win;
+    a.chunks = (const pgpu::SegsumChunk*)((const char*)dimage.p + at);
+    a.n_chunks = plan.chains.size();
+    a.out = o->prow(0);
+    a.partial = reg[0];
+    TimerScope t(dev, s, PGPU_KERNEL_SPMV, PGPU_FORM_SEQ);
+    if (!pgpu::launch_spmv(G, K, a, blocks_of((a.n_chunks + ipw - 1) / ipw), s))
+      return fail(PGPU_ERR_UNSUPPORTED, "spmv kernels not compiled for this key class");
+    HIP_TRY(hipGetLastError());
+    t.stop();
+    at += plan.chains.size() * sizeof(pgpu::SegsumChunk);
+  }
+  // the fold levels: the segmented sum's kernel over the partial rows (perm == null), in the form with the same limbs per
+  // half on more lanes where the level leaves SIMDs empty (2048-bit keys: (8,9))
+  const pgpu_pubkey::PubForm* wide = nullptr;
+  for (const auto& alt : key->hforms)
+    if (alt->H * alt->K == l2 && alt->H > G && pgpu::segsum_wide_has(alt->H, alt->K)) wide = alt.get();
+  for (size_t f = 0; f < plan.fold.levels.size(); ++f) {
+    const auto& lv = plan.fold.levels[f];
+    const pgpu_pubkey::PubForm* lf = wide && policy::segsum_wide_pays(wide->H, lv.chunks.size()) ? wide : pf;
+    pgpu::SegsumArgs a{};
+    a.ctx = hensel_pub_view(lf, dev.index);
+    a.src = reg[f & 1];
+    a.perm = nullptr;
+    a.chunks = (const pgpu::SegsumChunk*)((const char*)dimage.p + at);
+    a.n_chunks = lv.chunks.size();
+    a.out = o->prow(0);
+    a.partial = reg[(f + 1) & 1];
+    const size_t fipw = 64 / (size_t)lf->H, waves = (a.n_chunks + fipw - 1) / fipw;
+    TimerScope t(dev, s, PGPU_KERNEL_SPMV, PGPU_FORM_SEQ);
+    if (!pgpu::launch_segsum(lf->H, lf->K, a, blocks_of(waves), s))
+      return fail(PGPU_ERR_UNSUPPORTED, "segment sum kernels not compiled for this key class");
+    HIP_TRY(hipGetLastError());
+    t.stop();
+    at += lv.chunks.size() * sizeof(pgpu::SegsumChunk);
+  }
+  RC_TRY(lanes_order(w, x->lane, false));
+  *out = o.release();
+  return PGPU_OK;
+}
+
 // ---- encrypted segmented prefix sum (hensel_segscan.hpp; policy.hpp: segscan_*) ----
 int pgpu_ct_segment_scan_plan(int key_bits, size_t rows, size_t seg_len, int* chunk, int* levels, size_t* products) {
   if (key_bits < 1 || rows == 0 || seg_len == 0)

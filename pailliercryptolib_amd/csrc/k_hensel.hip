@@ -1,5 +1,5 @@
 // pailliercryptolib_amd -- instantiations of the split-form CRT-decrypt exponentiation (hensel.hpp), split over
-// PGPU_PART = 0..51 so that they compile in parallel (38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 45-47: the encrypted segmented prefix sum; 48-51: the encrypted slot packing; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
+// PGPU_PART = 0..55 so that they compile in parallel (53-55: the encrypted sparse matrix-vector product; 38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 45-47: the encrypted segmented prefix sum; 48-51: the encrypted slot packing; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
 // the two-wavefronts-per-SIMD build of the (2,19) decrypt form; 11-13: element-wise operations on pair rows).
 #include "hensel_seq.hpp"
 #include "launch.hpp"
@@ -27,9 +27,12 @@
 #if defined(PGPU_PART) && PGPU_PART >= 48 && PGPU_PART <= 51
 #include "hensel_pack.hpp"      // the encrypted slot packing: one Horner chain per output row
 #endif
+#if defined(PGPU_PART) && PGPU_PART >= 53 && PGPU_PART <= 55
+#include "hensel_spmv.hpp"      // the encrypted sparse matrix-vector product: one multi-exponentiation per chain of a CSR row
+#endif
 
 #ifndef PGPU_PART
-#error "compile with -DPGPU_PART=0..52 (15 and 30 are retired)"
+#error "compile with -DPGPU_PART=0..55 (15 and 30 are retired)"
 #endif
 
 namespace pgpu {
@@ -553,6 +556,26 @@ bool PGPU_SC_NAME(int G, int K, const SegscanArgs& a, unsigned blocks, hipStream
 bool PGPU_PK_NAME(int G, int K, const PackArgs& a, unsigned blocks, hipStream_t s) {
   if (G != PGPU_PK_G || K != PGPU_PK_K) return false;
   hipLaunchKernelGGL((pack_kernel<PGPU_PK_G, PGPU_PK_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
+  return true;
+}
+#elif PGPU_PART >= 53 && PGPU_PART <= 55
+// the encrypted sparse matrix-vector product (hensel_spmv.hpp): one geometry per part
+#if PGPU_PART == 53
+#define PGPU_SP_G 2
+#define PGPU_SP_K 19
+#define PGPU_SP_NAME launch_spmv_part53
+#elif PGPU_PART == 54
+#define PGPU_SP_G 4
+#define PGPU_SP_K 18
+#define PGPU_SP_NAME launch_spmv_part54
+#else
+#define PGPU_SP_G 8
+#define PGPU_SP_K 14
+#define PGPU_SP_NAME launch_spmv_part55
+#endif
+bool PGPU_SP_NAME(int G, int K, const SpmvArgs& a, unsigned blocks, hipStream_t s) {
+  if (G != PGPU_SP_G || K != PGPU_SP_K) return false;
+  hipLaunchKernelGGL((spmv_kernel<PGPU_SP_G, PGPU_SP_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
   return true;
 }
 #else

@@ -333,6 +333,25 @@ struct SegsumArgs {
   uint32_t* partial;         // [..][2*L2] partial rows this level writes
 };
 
+// Encrypted sparse matrix-vector product on pair rows (hensel_spmv.hpp): out[i] = prod_t x[col_idx[t]]^w[t] over the CSR
+// entries t of row i, as a multi-exponentiation per chain descriptor.  A chain walks the CSR positions begin .. begin +
+// len - 1 of ONE row and writes one row: dst as in SegsumChunk (a row of `out`, or with kSegsumPartial a row of `partial`,
+// which the fold levels -- segsum_kernel -- multiply together).  The table is matvec_table_kernel's, built from MatvecArgs.
+struct SpmvArgs {
+  HenselPubDev ctx;
+  const uint32_t* table;     // [cols][2^window][2*L2] T[j][d] = x[j]^d
+  const uint32_t* col_idx;   // [nnz] column of every CSR entry, each < cols; nnz >= 1
+  const uint64_t* w;         // [nnz][w_stride] the weights in CSR order; bits at and above e_bits are ignored
+  size_t w_stride;
+  int w_words;               // valid words per value
+  int e_bits;                // >= 1
+  int window;                // 1..6
+  const SegsumChunk* chunks; // [n_chunks], ordered by len descending; len 0: an empty row, the row of one
+  size_t n_chunks;           // >= 1
+  uint32_t* out;             // [rows][2*L2] the result batch
+  uint32_t* partial;         // [..][2*L2] partial rows of the rows cut into several chains
+};
+
 // Encrypted segmented prefix sum on pair rows (hensel_segscan.hpp): one product chain per chunk descriptor, EVERY
 // intermediate value stored.  A chunk walks the rows src[begin], src[begin + step], ..., src[begin + (len - 1) * step]
 // (step = +1 or -1, one value per launch) and writes the running product after entry t to out[begin + t * step].  carry

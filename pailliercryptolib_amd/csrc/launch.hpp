@@ -354,6 +354,18 @@ inline bool launch_pack(int G, int K, const PackArgs& a, unsigned blocks, hipStr
          launch_pack_part50(G, K, a, blocks, s) || launch_pack_part51(G, K, a, blocks, s);
 }
 
+// The encrypted sparse matrix-vector product (hensel_spmv.hpp; k_hensel.hip parts 53-55): one multi-exponentiation per
+// chain of a CSR row over the window tables of launch_matvec_table, in the geometries matvec_has lists (no (8,9) form:
+// the fold levels, which run through launch_segsum, have one)
+inline bool spmv_has(int G, int K) { return matvec_has(G, K); }
+bool launch_spmv_part53(int G, int K, const SpmvArgs& a, unsigned blocks, hipStream_t s);
+bool launch_spmv_part54(int G, int K, const SpmvArgs& a, unsigned blocks, hipStream_t s);
+bool launch_spmv_part55(int G, int K, const SpmvArgs& a, unsigned blocks, hipStream_t s);
+inline bool launch_spmv(int G, int K, const SpmvArgs& a, unsigned blocks, hipStream_t s) {
+  return launch_spmv_part53(G, K, a, blocks, s) || launch_spmv_part54(G, K, a, blocks, s) ||
+         launch_spmv_part55(G, K, a, blocks, s);
+}
+
 // DJN encrypt to pair rows in the same form (k_hensel.hip parts 20, 21, 28): (4,18) 2048-bit keys, (8,14) 3072, (2,19) 1024
 inline bool hensel_fb_encrypt_seq_has(int G, int K) { return (G == 4 && K == 18) || (G == 8 && K == 14) || (G == 2 && K == 19); }
 bool launch_hensel_fb_encrypt_seq_part28(int G, int K, const HenselFbArgs& a, unsigned blocks, hipStream_t s);

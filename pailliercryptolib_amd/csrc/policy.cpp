@@ -364,6 +364,96 @@ void segsum_plan(const std::vector<size_t>& offsets, int chunk, SegsumPlan* plan
 }
 
 
+// ---- encrypted sparse matrix-vector product ----
+int spmv_chunk(int G, size_t nnz, size_t rows) {
+  (void)rows;
+  const long forced = env_now("PGPU_SPMV_CHUNK");
+  if (forced >= 1) return (int)std::min(forced, (long)kSegsumForcedMax);
+  const size_t chains = kSegsumWavesPerSimd * kSimds * (64 / (size_t)G);   // chains that fill the chip
+  return (int)std::max(kSpmvMinChunk, std::min(kSpmvMaxChunk, nnz / chains));
+}
+// the chunk of the fold levels: the chains' own, but a fold by 1 would never end
+static int spmv_fold_chunk(int chunk) { return std::max(2, chunk); }
+int spmv_levels(int chunk, size_t longest) {
+  const size_t c = (size_t)chunk;
+  return longest <= c ? 1 : 1 + segsum_levels(spmv_fold_chunk(chunk), (longest + c - 1) / c);
+}
+bool spmv_plan(const uint64_t* row_ptr, size_t rows, int chunk, SpmvPlan* plan) {
+  constexpr size_t kMax = (size_t)1 << 31;
+  const size_t c = (size_t)chunk;
+  if (!row_ptr || rows == 0 || rows >= kMax || chunk < 1 || row_ptr[0] != 0) return false;
+  size_t n_chains = 0, longest = 0;
+  for (size_t i = 0; i < rows; ++i) {
+    if (row_ptr[i + 1] < row_ptr[i] || row_ptr[i + 1] >= kMax) return false;
+    const size_t m = (size_t)(row_ptr[i + 1] - row_ptr[i]);
+    n_chains += std::max<size_t>(1, (m + c - 1) / c);
+    longest = std::max(longest, m);
+    if (n_chains >= kMax) return false;
+  }
+  plan->chunk = chunk;
+  plan->longest = longest;
+  plan->partial_rows = 0;
+  plan->chains.clear();
+  plan->chains.reserve(n_chains);
+  // the rows of several chains, as segments of the partial rows for the fold
+  std::vector<size_t> fold_offsets(1, 0);
+  std::vector<uint32_t> fold_row;
+  for (size_t i = 0; i < rows; ++i) {
+    const size_t begin = (size_t)row_ptr[i], m = (size_t)(row_ptr[i + 1] - row_ptr[i]);
+    if (m <= c) {
+      plan->chains.push_back({(uint64_t)begin, (uint32_t)m, (uint32_t)i});
+      continue;
+    }
+    const size_t parts = (m + c - 1) / c;
+    for (size_t k = 0; k < parts; ++k)
+      plan->chains.push_back({(uint64_t)(begin + k * c), (uint32_t)std::min(c, m - k * c),
+                              kSegsumPartial | (uint32_t)(plan->partial_rows + k)});
+    plan->partial_rows += parts;
+    fold_offsets.push_back(plan->partial_rows);
+    fold_row.push_back((uint32_t)i);
+  }
+  plan->n_chains = plan->chains.size();
+  // by len descending, equal lengths in the order made above: a counting sort (len <= chunk <= kSegsumForcedMax)
+  {
+    std::vector<size_t> at(c + 2, 0);
+    for (const SegsumChunk& k : plan->chains) ++at[c - k.len + 1];
+    for (size_t i = 0; i <= c; ++i) at[i + 1] += at[i];
+    std::vector<SegsumChunk> sorted(plan->chains.size());
+    for (const SegsumChunk& k : plan->chains) sorted[at[c - k.len]++] = k;
+    plan->chains.swap(sorted);
+  }
+  // the fold: a segmented sum over the partial rows, segment s being row fold_row[s] of the result
+  segsum_plan(fold_offsets, spmv_fold_chunk(chunk), &plan->fold);
+  for (SegsumLevel& lv : plan->fold.levels)
+    for (SegsumChunk& k : lv.chunks)
+      if (!(k.dst & kSegsumPartial)) k.dst = fold_row[k.dst];
+  return true;
+}
+double spmv_products(size_t rows, size_t cols, size_t nnz, size_t chains, int e_bits, int w) {
+  const double nwin = (double)((e_bits + w - 1) / w);
+  return (double)cols * (double)(((size_t)1 << w) - 2) + (double)chains * (double)e_bits + (double)nnz * nwin +
+         (double)(chains - std::min(chains, rows));
+}
+int spmv_window(size_t rows, size_t cols, size_t nnz, size_t chains, int e_bits, size_t row_bytes) {
+  const long forced = env_now("PGPU_SPMV_WINDOW");
+  if (forced > 0) return (int)std::min(forced, 6L);
+  int best = 1;
+  double best_cost = spmv_products(rows, cols, nnz, chains, e_bits, 1);
+  for (int w = 2; w <= 6; ++w) {
+    if ((double)cols * (double)((size_t)1 << w) * (double)row_bytes > (double)kMatvecTableCap) break;
+    const double cost = spmv_products(rows, cols, nnz, chains, e_bits, w);
+    if (cost < best_cost) { best_cost = cost; best = w; }
+  }
+  return best;
+}
+size_t spmv_chains_estimate(size_t rows, size_t nnz, size_t longest, int chunk) {
+  const size_t c = (size_t)chunk, cut = [c](size_t m) { return std::max<size_t>(1, (m + c - 1) / c); }(longest);
+  if (rows <= 1) return cut;
+  const size_t rest = nnz > longest ? nnz - longest : 0, avg = (rest + rows - 2) / (rows - 1);
+  return cut + (rows - 1) * std::max<size_t>(1, (avg + c - 1) / c);
+}
+
+
 // ---- encrypted segmented prefix sum ----
 int segscan_chunk(int G, size_t rows, size_t seg_len) {
   const long forced = env_now("PGPU_SEGSCAN_CHUNK");

@@ -183,6 +183,57 @@ struct SegsumPlan {
 void segsum_plan(const std::vector<size_t>& offsets, int chunk, SegsumPlan* plan);
 
 
+// ---- the encrypted sparse matrix-vector product (hensel_spmv.hpp; pgpu_batch_ct_spmv, pgpu_ct_spmv_plan) ----
+// out[i] = prod_t X[col_idx[t]]^w[t] over the CSR entries t of row i: the window tables of the matvec shared by all rows,
+// one group of G lanes per CHAIN of at most `chunk` consecutive CSR entries of one row.  Counted in pair products a row of
+// m entries cut into c = max(1, ceil(m / chunk)) chains costs
+//     c * e_bits               squarings (every chain runs its own)
+//   + m * ceil(e_bits / w)     multiplications by table entries
+//   + (c - 1)                  fold of the partial products,
+// and the table cols * (2^w - 2) once.  (As in matvec_products the top window's w squarings, which no chain runs, and the
+// product the first entry of a chain saves are counted all the same.)
+// 1. the chunk: the one that gives every SIMD kSegsumWavesPerSimd wavefronts of 64/G chains, nnz / (that many chains), but
+//    * at least kSpmvMinChunk = kMatvecMinSliceCols entries, section 11's reason: the e_bits squarings a chain repeats stay
+//      at most w / (w + kSpmvMinChunk) of its products;
+//    * at most kSpmvMaxChunk = kSegsumMaxChunk entries: one very long row does not become one serial chain.
+//    `rows` bounds nothing yet: a matrix of many short rows has its chains given by the rows, whatever the chunk.
+//    All three constants are CARRIED OVER from sections 11 and 12, not fitted to this kernel.  The one sweep of
+//    PGPU_SPMV_CHUNK made so far (profiles/spmv_bench.txt: 2^20 non-zeros, 2048-bit key) confirms the
+//    fill on 1024 rows of about 1024 entries, finds rows of exactly 16 entries 6 % faster uncut -- here a cut costs e_bits
+//    squarings, which the rule does not weigh -- and reaches neither the floor's nor the ceiling's reason.
+//    PGPU_SPMV_CHUNK=c, 1 <= c <= kSegsumForcedMax, forces it (larger values are clamped; read at every call: the tests
+//    reach every path with it).
+constexpr size_t kSpmvMinChunk = kMatvecMinSliceCols;
+constexpr size_t kSpmvMaxChunk = kSegsumMaxChunk;
+int spmv_chunk(int G, size_t nnz, size_t rows);
+// 2. the plan.  chains: level 0, one descriptor per chain -- begin: a CSR position, dst: the output row, or kSegsumPartial |
+//    a partial row when the row has several chains; an empty row is a chain of length 0 -- ordered by len descending
+//    (stable).  fold: exactly what segsum_plan makes of a segmented sum over those partial rows (rows of one chain appear
+//    there as empty segments and are dropped: their result is already written); fold.levels may be empty.
+//    The fold runs with the chains' own chunk (at least 2).  false: row_ptr does not start at 0 or decreases, or rows, nnz or
+//    the chains reach 2^31, more than the fields of a descriptor address (nothing is written then).
+struct SpmvPlan {
+  int chunk = 0;
+  size_t longest = 0;                 // entries of the longest row
+  size_t n_chains = 0;                // == chains.size()
+  size_t partial_rows = 0;            // rows the spmv launch writes for the fold levels
+  std::vector<SegsumChunk> chains;
+  SegsumPlan fold;
+};
+bool spmv_plan(const uint64_t* row_ptr, size_t rows, int chunk, SpmvPlan* plan);
+//    launches of the call without the table build: 1 + fold levels, from the longest row alone
+int spmv_levels(int chunk, size_t longest);
+// 3. products of the schedule for given totals (chains: over all rows), table included; and the window: w in 1..6 with the
+//    fewest products among those whose table (cols * 2^w rows of row_bytes: EVERY column of x, referenced or not) stays
+//    under kMatvecTableCap.  PGPU_SPMV_WINDOW=w forces it.
+double spmv_products(size_t rows, size_t cols, size_t nnz, size_t chains, int e_bits, int w);
+int spmv_window(size_t rows, size_t cols, size_t nnz, size_t chains, int e_bits, size_t row_bytes);
+//    chains of a matrix of which only rows, nnz and the longest row are known (the plan call): the longest row cut by the
+//    chunk, the other rows taken as equally long -- exact while no row is longer than the chunk and for rows of one length,
+//    an estimate otherwise
+size_t spmv_chains_estimate(size_t rows, size_t nnz, size_t longest, int chunk);
+
+
 // ---- the encrypted segmented prefix sum (hensel_segscan.hpp; pgpu_batch_ct_segment_scan, pgpu_ct_segment_scan_plan) ----
 // out[r][t] = prod_{u <= t} X[r][u] (reverse: u >= t), x read as [rows][seg_len].  One chain of one group of G lanes
 // scans a row of m entries with m - 1 products, which is all the work there is; a row longer than the chunk is scanned by

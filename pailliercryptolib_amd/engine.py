@@ -179,6 +179,44 @@ class PublicKey:
                     L.pgpu_batch_destroy(h)
         return limbs_to_ints(out)
 
+    def spmv(self, x, indptr, indices, w, e_bits=None):
+        """Encrypted sparse matrix-vector product: x a list of ciphertexts (ints modulo n^2), the plaintext matrix in CSR
+        form -- indptr (rows + 1 offsets, starting at 0), indices (a column of x per entry), w (a non-negative int per
+        entry) -> the list of ciphertexts prod_t x[indices[t]]^w[t] mod n^2 over the entries t of every row, i.e.
+        encryptions of (A @ m) mod n; an empty row gives 1.  A weighted group-by SUM(v * x) GROUP BY id is the CSR with
+        indices = argsort(ids, stable), w = v[indices], indptr = the running count of every id.  One pgpu_batch_ct_spmv
+        call on resident batches (a shared-table multi-exponentiation per chain of a row); there is no element-wise
+        fall-back."""
+        indptr, indices, flat = [int(v) for v in indptr], [int(v) for v in indices], [int(v) for v in w]
+        cols, rows = len(x), len(indptr) - 1
+        if cols == 0 or rows < 1 or not flat or len(indices) != len(flat) or indptr[0] != 0 or indptr[-1] != len(flat):
+            raise RuntimeError("spmv error: Size mismatch!")
+        if any(b < a for a, b in zip(indptr, indptr[1:])):
+            raise RuntimeError("spmv error: indptr must be non-decreasing")
+        if min(indices) < 0 or max(indices) >= cols:
+            raise RuntimeError("spmv error: a column index is not below len(x)")
+        if min(flat) < 0:
+            raise RuntimeError("spmv error: negative weights have no encoding (pass w mod n)")
+        if e_bits is None:
+            e_bits = max(1, max(v.bit_length() for v in flat))
+        ew = (int(e_bits) + 63) // 64
+        L = _capi.lib()
+        W = 2 * self.n_words
+        hx, hw, ho = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        try:
+            xa, wa = ints_to_limbs([int(v) for v in x], W), ints_to_limbs(flat, ew)
+            rp, ci = np.array(indptr, dtype=np.uint64), np.array(indices, dtype=np.uint32)
+            _capi.check(L.pgpu_batch_upload(_ptr(xa), cols, W, W, ctypes.byref(hx)))
+            _capi.check(L.pgpu_batch_upload(_ptr(wa), len(flat), ew, ew, ctypes.byref(hw)))
+            _capi.check(L.pgpu_batch_ct_spmv(self._h, hx, _ptr(rp), _ptr(ci), hw, rows, int(e_bits), ctypes.byref(ho)))
+            out = np.empty((rows, W), dtype=np.uint64)
+            _capi.check(L.pgpu_batch_download(ho, _ptr(out)))
+        finally:
+            for h in (hx, hw, ho):
+                if h:
+                    L.pgpu_batch_destroy(h)
+        return limbs_to_ints(out)
+
     def segment_sum(self, x, ids, n_segments):
         """Encrypted segmented sum: x a list of ciphertexts (ints modulo n^2), ids one flat list of segment numbers (one
         group) or a list of such lists (several groupings of the same x); None leaves an element out of that group ->
