@@ -16,6 +16,8 @@ namespace ext {   // include/ipcl/ext/linear.hpp
 CipherText matVec(const PlainText& w, std::size_t rows, const CipherText& x);
 CipherText sparseMatVec(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx, const PlainText& w,
                         const CipherText& x);
+CipherText weightedSum(const std::vector<CipherText>& xs, const PlainText& w);
+CipherText sum(const std::vector<CipherText>& xs);
 // include/ipcl/ext/aggregate.hpp
 CipherText segmentSum(const CipherText& x, const std::vector<uint32_t>& ids, std::size_t n_segments, std::size_t groups);
 CipherText segmentScan(const CipherText& x, std::size_t seg_len, bool reverse);
@@ -53,6 +55,10 @@ class CipherText : public BaseText {
   // prod_t this[col_idx[t]]^w[t] over the CSR entries t of every row: csrc/host/linear.cpp
   CipherText sparseLinearMap(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx,
                              const PlainText& w) const;
+  friend CipherText ext::weightedSum(const std::vector<CipherText>& xs, const PlainText& w);
+  friend CipherText ext::sum(const std::vector<CipherText>& xs);
+  // prod_k xs[k][i]^w[k] (w == null: every weight 1), one weight per CipherText: csrc/host/linear.cpp
+  static CipherText weightedSumMap(const std::vector<CipherText>& xs, const PlainText* w);
   friend CipherText ext::segmentSum(const CipherText& x, const std::vector<uint32_t>& ids, std::size_t n_segments,
                                     std::size_t groups);
   // prod_{j: ids[g][j] == s} this[j]: csrc/host/aggregate.cpp

@@ -12,6 +12,12 @@
 //                        column named twice contributes twice, an empty row yields an encryption of 0 (the ciphertext 1).
 //                        One pgpu_batch_ct_spmv call: the window tables of the x[j] shared by all rows, the squarings
 //                        shared by the terms of a chain of a row.
+//   weightedSum(xs, w)   y[i] = sum_k w[k] * xs[k][i] under the encryption, ACROSS K CipherTexts of one size with one
+//                        plaintext weight per CipherText: Y[i] = prod_k X_k[i]^w[k] mod n^2 -- a federated average over K
+//                        clients' encrypted vectors.  A zero weight contributes nothing; all weights zero yield
+//                        encryptions of 0 (the ciphertext 1).  One pgpu_batch_ct_weighted_sum call: one bit-serial
+//                        schedule for all elements, the squarings shared by the K terms, no intermediate CipherText.
+//   sum(xs)              the case of every weight 1
 //
 // w: rows*cols non-negative plaintext weights, row-major (negative numbers have no encoding in the reference either; pass
 // w mod n).  One fused launch sequence on the GPU (pgpu_batch_ct_matvec: window tables of the x[j] shared by all rows, the
@@ -36,6 +42,8 @@ CipherText matVec(const PlainText& w, std::size_t rows, const CipherText& x);
 CipherText dot(const PlainText& w, const CipherText& x);
 CipherText sparseMatVec(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx, const PlainText& w,
                         const CipherText& x);
+CipherText weightedSum(const std::vector<CipherText>& xs, const PlainText& w);
+CipherText sum(const std::vector<CipherText>& xs);
 
 }  // namespace ext
 }  // namespace ipcl

@@ -431,6 +431,40 @@ int pgpu_batch_ct_spmv(const pgpu_pubkey* key, const pgpu_batch* x, const uint64
  * e_bits < 1, rows or nnz of 2^31 or more.  PGPU_ERR_UNSUPPORTED: no pair rows for keys of key_bits. */
 int pgpu_ct_spmv_plan(int key_bits, size_t rows, size_t cols, size_t nnz, size_t longest_row, int e_bits,
                       int* window, int* chunk, int* levels, size_t* table_bytes, size_t* products);
+/* Encrypted weighted sum of K resident batches (a federated average: K clients send one encrypted vector each, the server
+ * aggregates ACROSS them): xs[k] resident ciphertext batches of one common count under `key` (pair rows, or uploaded plain
+ * ciphertext words: converted on the way in; any mix within one call), one plaintext weight per BATCH:
+ *     out[i] = prod_k xs[k][i]^(a_k) mod n^2
+ *     i.e. Dec(out[i]) = sum_k a_k * Dec(xs[k][i]) mod n
+ * weights: HOST words, [n_terms][w_words] little-endian, of any width up to w_words words (a mod n for a negative a is a
+ * legal, full-width weight), consumed before the call returns; NULL: every weight is 1, the plain sum.  The device never
+ * reads them: the host turns them into one bit-serial schedule that is the same for every element -- one squaring per bit
+ * below the top one, one product per set bit, nothing for a zero bit, the squarings shared by all K terms -- and cuts the
+ * terms into slices that run side by side where the elements alone leave the chip empty, folded by one more launch
+ * ("Encrypted weighted sum of K resident batches").  The same handle may appear more than once and contributes
+ * once per appearance; a zero weight contributes 1 and its batch is never read; if every weight is zero every row is the
+ * ciphertext 1, as an empty segment and an empty spmv row are; n_terms == 1 with weight 1 is a copy.  The result is an
+ * ordinary resident ciphertext batch of count elements in pair rows on the lane of xs[0] (operands of other lanes are
+ * ordered in by events, as for pgpu_batch_ct_add); every xs[k] is left unchanged.
+ * PGPU_ERR_INVALID_PARAM: null / stale handles, n_terms == 0 or above 65535, counts that differ, ciphertext width
+ * mismatch, a batch of another key, w_words < 1 with non-null weights, a schedule of 2^31 steps or more.
+ * PGPU_ERR_UNSUPPORTED: keys without pair rows (beyond 3072 bits; PGPU_PAIR_ROWS=0 / PGPU_HENSEL=0), pools of more than one
+ * GPU, and -- SIDE CHANNELS -- the masked table-gather policy: the schedule and the row addresses depend on the caller's
+ * PLAINTEXT weights only (never on key material or on anything encrypted); with pgpu_set_table_gather_policy(1) the call
+ * is refused all the same, which keeps one rule for the aggregation calls.
+ * All refusals are decided on the host before any launch and leave *out untouched; there is no element-wise fall-back. */
+int pgpu_batch_ct_weighted_sum(const pgpu_pubkey* key, const pgpu_batch* const* xs, size_t n_terms,
+                               const uint64_t* weights /* HOST, [n_terms][w_words] little-endian, or NULL: all ones */,
+                               int w_words, pgpu_batch** out);
+/* What a call of this shape would run (host-side query, needs no device).  lanes, limbs: the (G, K) form of the first
+ * launch; slices: the non-empty slices of the terms (1: one launch; more: one launch over all slices plus one fold
+ * launch); steps: the schedule length of the longest slice; products: the pair products of the call, count * ((bits - 1)
+ * squarings + (set bits - 1) products per slice + (slices - 1) for the fold) -- exact, padding excluded.  The rule is
+ * policy.hpp: wsum_*; PGPU_WSUM_SLICES=s / PGPU_WSUM_WIDE=0|1 force the slices and the form, read at every call.
+ * PGPU_ERR_INVALID_PARAM: key_bits < 1, count == 0, n_terms == 0 or above 65535, w_words < 1 with non-null weights, a
+ * schedule of 2^31 steps or more, a product count beyond size_t.  PGPU_ERR_UNSUPPORTED: no pair rows for keys of key_bits. */
+int pgpu_ct_weighted_sum_plan(int key_bits, size_t count, size_t n_terms, const uint64_t* weights_or_null, int w_words,
+                              int* lanes, int* limbs, int* slices, size_t* steps, size_t* products);
 
 /* ---- instrumentation used by bench.py (roofline) ----
  * With timing enabled every kernel launch is bracketed by two HIP events recorded on the stream
@@ -446,7 +480,8 @@ typedef enum pgpu_kernel_kind {
   PGPU_KERNEL_SEGSUM = 6,     /* every launch of pgpu_batch_ct_segment_sum: one per level */
   PGPU_KERNEL_SEGSCAN = 7,    /* every launch of pgpu_batch_ct_segment_scan: up-sweeps (segsum_kernel) and scans */
   PGPU_KERNEL_PACK = 8,       /* the launch of pgpu_batch_ct_pack */
-  PGPU_KERNEL_SPMV = 9        /* every launch of pgpu_batch_ct_spmv: table build, multi-exponentiation, fold levels */
+  PGPU_KERNEL_SPMV = 9,       /* every launch of pgpu_batch_ct_spmv: table build, multi-exponentiation, fold levels */
+  PGPU_KERNEL_WSUM = 10       /* every launch of pgpu_batch_ct_weighted_sum: the slices' schedules, the fold */
 } pgpu_kernel_kind;
 int pgpu_set_timing(int enabled);
 int pgpu_timing_collect(int* kinds, double* ms, int max_entries);

@@ -40,6 +40,7 @@ SYMBOLS = [
     "pgpu_batch_ct_segment_scan", "pgpu_ct_segment_scan_plan",
     "pgpu_batch_ct_pack", "pgpu_ct_pack_plan",
     "pgpu_batch_ct_spmv", "pgpu_ct_spmv_plan",
+    "pgpu_batch_ct_weighted_sum", "pgpu_ct_weighted_sum_plan",
 ]
 FEATURE_4096_SPLIT = 1
 SEGMENT_NONE = 0xFFFFFFFF      # PGPU_SEGMENT_NONE: the element is left out of that group
@@ -192,6 +193,11 @@ def lib():
     L.pgpu_ct_spmv_plan.argtypes = [c_int, c_size_t, c_size_t, c_size_t, c_size_t, c_int, POINTER(c_int), POINTER(c_int),
                                     POINTER(c_int), POINTER(c_size_t), POINTER(c_size_t)]
     L.pgpu_ct_spmv_plan.restype = c_int
+    L.pgpu_batch_ct_weighted_sum.argtypes = [c_void_p, POINTER(c_void_p), c_size_t, c_void_p, c_int, POINTER(c_void_p)]
+    L.pgpu_batch_ct_weighted_sum.restype = c_int
+    L.pgpu_ct_weighted_sum_plan.argtypes = [c_int, c_size_t, c_size_t, c_void_p, c_int, POINTER(c_int), POINTER(c_int),
+                                            POINTER(c_int), POINTER(c_size_t), POINTER(c_size_t)]
+    L.pgpu_ct_weighted_sum_plan.restype = c_int
     _lib = L
     return L
 

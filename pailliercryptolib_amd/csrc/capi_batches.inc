@@ -989,6 +989,171 @@ int pgpu_batch_ct_spmv(const pgpu_pubkey* key, const pgpu_batch* x, const uint64
   return PGPU_OK;
 }
 
+// ---- encrypted weighted sum of K resident batches (hensel_wsum.hpp; policy.hpp: wsum_*) ----
+int pgpu_ct_weighted_sum_plan(int key_bits, size_t count, size_t n_terms, const uint64_t* weights_or_null, int w_words,
+                              int* lanes, int* limbs, int* slices, size_t* steps, size_t* products) {
+  if (key_bits < 1 || count == 0 || n_terms == 0 || n_terms > policy::kWsumMaxTerms || (weights_or_null && w_words < 1))
+    return fail(PGPU_ERR_INVALID_PARAM, "weighted sum plan: key_bits, count and n_terms must be positive, n_terms at most 65535, "
+                                        "w_words positive where weights are given");
+  int G = 0, K = 0;
+  if (!policy::matvec_geometry(key_bits, &G, &K))
+    return fail(PGPU_ERR_UNSUPPORTED, "weighted sum: keys of this size have no pair rows (1024- to 3072-bit key classes only)");
+  policy::WsumPlan plan;
+  if (!policy::wsum_plan(weights_or_null, w_words, n_terms, policy::wsum_slices(G, count, n_terms, !weights_or_null), &plan))
+    return fail(PGPU_ERR_INVALID_PARAM, "weighted sum plan: a schedule of 2^31 steps or more");
+  if (plan.products && count > ~(size_t)0 / plan.products)
+    return fail(PGPU_ERR_INVALID_PARAM, "weighted sum plan: the product count overflows");
+  policy::wsum_geometry(key_bits, count * plan.slices.size(), &G, &K);
+  if (lanes) *lanes = G;
+  if (limbs) *limbs = K;
+  if (slices) *slices = (int)plan.slices.size();
+  if (steps) *steps = plan.longest;
+  if (products) *products = count * plan.products;
+  return PGPU_OK;
+}
+
+int pgpu_batch_ct_weighted_sum(const pgpu_pubkey* key, const pgpu_batch* const* xs, size_t n_terms, const uint64_t* weights,
+                               int w_words, pgpu_batch** out) {
+  RC_TRY(rt::check_ready());
+  if (!key || !xs || !out) return fail(PGPU_ERR_INVALID_PARAM, "null argument");
+  RC_TRY(check_gen(key->gen, "key"));
+  if (n_terms == 0 || n_terms > policy::kWsumMaxTerms)
+    return fail(PGPU_ERR_INVALID_PARAM, "weighted sum error: n_terms must be between 1 and 65535");
+  if (weights && w_words < 1) return fail(PGPU_ERR_INVALID_PARAM, "weighted sum error: w_words must be positive");
+  const int W = 2 * key->n_words;
+  for (size_t k = 0; k < n_terms; ++k) {
+    if (!xs[k]) return fail(PGPU_ERR_INVALID_PARAM, "null argument");
+    RC_TRY(check_gen(xs[k]->gen, "batch"));
+  }
+  const size_t count = xs[0]->count;
+  if (count == 0) return fail(PGPU_ERR_INVALID_PARAM, "weighted sum error: empty batch");
+  for (size_t k = 0; k < n_terms; ++k) {
+    if (xs[k]->count != count) return fail(PGPU_ERR_INVALID_PARAM, "weighted sum error: Size mismatch! (every batch must hold count(xs[0]) elements)");
+    if (xs[k]->words != W) return fail(PGPU_ERR_INVALID_PARAM, "weighted sum error: ciphertext width mismatch");
+    if (!same_domain(xs[k]->mont, key->nsq)) return fail(PGPU_ERR_INVALID_PARAM, "weighted sum error: batch belongs to a different key");
+  }
+  if (rt::pool_size() > 1)
+    return fail(PGPU_ERR_UNSUPPORTED, "weighted sum: pools of more than one GPU are not supported (elements are not sharded yet)");
+  const pgpu_pubkey::PubForm* pf = pair_form(key);
+  if (!pf || !pgpu::matvec_has(pf->H, pf->K))
+    return fail(PGPU_ERR_UNSUPPORTED, "weighted sum: key has no pair form (1024- to 3072-bit keys; PGPU_PAIR_ROWS=0 / PGPU_HENSEL=0 switch it off)");
+  // the schedule and the row addresses depend on the caller's PLAINTEXT weights only (never on key material or on anything
+  // encrypted); the call is refused under the masked policy all the same, like its siblings: one rule for the aggregation calls
+  if (g_ct_gather.load())
+    return fail(PGPU_ERR_UNSUPPORTED, "weighted sum: the masked table-gather policy is on (pgpu_set_table_gather_policy / PGPU_CT_GATHER); "
+                                      "the schedule and the row addresses depend on the caller's plaintext weights only, but "
+                                      "the aggregation calls on resident ciphertexts have no masked variant");
+  for (size_t k = 0; k < n_terms; ++k)
+    if (xs[k]->pair_l2 && (xs[k]->pair_l2 != pf->H * pf->K || !(xs[k]->pair_form->n == key->n)))
+      return fail(PGPU_ERR_INVALID_PARAM, "weighted sum error: batch belongs to a different key");
+  // the schedule, on the host: the slices of the terms, then the fold over their partial rows
+  const int G = pf->H, l2 = G * pf->K;
+  const size_t LQ = (size_t)2 * l2, row_bytes = LQ * sizeof(uint32_t);
+  policy::WsumPlan plan, fold;
+  if (!policy::wsum_plan(weights, w_words, n_terms, policy::wsum_slices(G, count, n_terms, !weights), &plan))
+    return fail(PGPU_ERR_INVALID_PARAM, "weighted sum error: a schedule of 2^31 steps or more");
+  const size_t S = plan.slices.size();
+  if (S > 1) policy::wsum_plan(nullptr, 0, S, 1, &fold);
+  // the operands as pair rows, every used batch converted once on its own lane; a batch of weight zero is never read
+  std::vector<char> used(n_terms, 0);
+  if (!plan.all_zero)
+    for (const pgpu::WsumSlice& sl : plan.slices) {
+      used[sl.first] = 1;
+      for (size_t t = 0; t < sl.n_steps; ++t) {
+        const pgpu::WsumStep& st = plan.steps[(size_t)sl.step_begin + t];
+        if (st.op != pgpu::kWsumSqr) used[st.op] = 1;
+      }
+    }
+  std::vector<std::unique_ptr<pgpu_batch>> tmps;
+  std::map<const pgpu_batch*, const pgpu_batch*> pair_of;    // (the same handle may appear more than once)
+  for (size_t k = 0; k < n_terms; ++k) {
+    if (!used[k] || pair_of.count(xs[k])) continue;
+    const pgpu_batch* p = nullptr;
+    std::unique_ptr<pgpu_batch> t;
+    RC_TRY(as_pair_batch(key, xs[k], &p, &t));
+    if (t) tmps.push_back(std::move(t));
+    pair_of[xs[k]] = p;
+  }
+  const int lane = xs[0]->lane;
+  std::unique_ptr<pgpu_batch> o;
+  RC_TRY(new_batch(count, W, &o, l2, lane));
+  o->pair_form = pair_form_shared(key);
+  rt::Device& dev = rt::device(0);
+  rt::DeviceGuard g(dev.ordinal);
+  hipStream_t s = dev.bs(lane);
+  for (const auto& kv : pair_of) RC_TRY(lanes_order(kv.second, lane, true));
+  // one image for the device: the row bases, the slice descriptors of both launches, their step lists
+  rt::DevMem dimage, partial;
+  if (S > 1) RC_TRY(partial.alloc(dev, s, (S - 1) * count * row_bytes));
+  const size_t tab_bytes = n_terms * sizeof(uint32_t*), ftab_bytes = (S > 1 ? S : 0) * sizeof(uint32_t*);
+  const size_t sl_at = tab_bytes + ftab_bytes, fsl_at = sl_at + S * sizeof(pgpu::WsumSlice);
+  const size_t st_at = fsl_at + fold.slices.size() * sizeof(pgpu::WsumSlice);
+  const size_t fst_at = st_at + plan.steps.size() * sizeof(pgpu::WsumStep);
+  const size_t image_bytes = fst_at + fold.steps.size() * sizeof(pgpu::WsumStep);
+  std::vector<char> image(image_bytes, 0);
+  {
+    // every entry of the table is addressable: a batch that no step names stands in as the result batch itself
+    std::vector<const uint32_t*> tab(n_terms, o->prow(0)), ftab;
+    for (size_t k = 0; k < n_terms; ++k)
+      if (used[k]) tab[k] = pair_of[xs[k]]->prow(0);
+    std::memcpy(image.data(), tab.data(), tab_bytes);
+    // slice 0 writes the result batch, the others a partial region each; the fold multiplies them into the result batch in
+    // place (a group reads row i of every region before it stores row i, and no other live group touches that row)
+    for (size_t j = 0; j < S; ++j) {
+      plan.slices[j].dst = j == 0 ? o->prow(0) : (uint32_t*)partial.p + (j - 1) * count * LQ;
+      ftab.push_back(plan.slices[j].dst);
+    }
+    if (S > 1) {
+      std::memcpy(image.data() + tab_bytes, ftab.data(), ftab_bytes);
+      fold.slices[0].dst = o->prow(0);
+      std::memcpy(image.data() + fsl_at, fold.slices.data(), sizeof(pgpu::WsumSlice));
+      std::memcpy(image.data() + fst_at, fold.steps.data(), fold.steps.size() * sizeof(pgpu::WsumStep));
+    }
+    std::memcpy(image.data() + sl_at, plan.slices.data(), S * sizeof(pgpu::WsumSlice));
+    if (!plan.steps.empty()) std::memcpy(image.data() + st_at, plan.steps.data(), plan.steps.size() * sizeof(pgpu::WsumStep));
+  }
+  RC_TRY(dimage.alloc(dev, s, image_bytes));
+  if (image_bytes <= kBounceBytes) {
+    Bounce& bn = bounce();
+    RC_TRY(bn.ready());
+    std::memcpy(bn.p, image.data(), image_bytes);
+    HIP_TRY(hipMemcpyAsync(dimage.p, bn.p, image_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(bn.ev, s));
+    bn.pending = true;
+  } else {   // through a worker lane's staging buffers, queued on the same stream: nothing is waited for
+    rt::TaskGroup tg;
+    void* dst = dimage.p;
+    const char* src = image.data();
+    tg.run(dev, [=](rt::Lane& ln) -> int { return ln.h2d(dst, src, image_bytes, s); });
+    RC_TRY(tg.wait());
+  }
+  // the form with the same limbs per half on more lanes, for launches that leave SIMDs empty (policy.hpp: wsum_wide_pays)
+  const pgpu_pubkey::PubForm* wide = nullptr;
+  for (const auto& alt : key->hforms)
+    if (alt->H * alt->K == l2 && alt->H > G && pgpu::wsum_wide_has(alt->H, alt->K)) wide = alt.get();
+  auto launch = [&](size_t tab_off, size_t slices_off, size_t steps_off, size_t n_slices) -> int {
+    const pgpu_pubkey::PubForm* lf = wide && policy::wsum_wide_pays(wide->H, count * n_slices) ? wide : pf;
+    pgpu::WsumArgs a{};
+    a.ctx = hensel_pub_view(lf, dev.index);
+    a.rows = (const uint32_t* const*)((const char*)dimage.p + tab_off);
+    a.slices = (const pgpu::WsumSlice*)((const char*)dimage.p + slices_off);
+    a.steps = (const pgpu::WsumStep*)((const char*)dimage.p + steps_off);
+    a.count = count;
+    const size_t ipw = 64 / (size_t)lf->H, waves = (count + ipw - 1) / ipw;
+    TimerScope t(dev, s, PGPU_KERNEL_WSUM, PGPU_FORM_SEQ);
+    if (!pgpu::launch_wsum(lf->H, lf->K, a, (unsigned)((waves + pgpu::kWavesPerWG - 1) / pgpu::kWavesPerWG), (unsigned)n_slices, s))
+      return fail(PGPU_ERR_UNSUPPORTED, "weighted sum kernels not compiled for this key class");
+    HIP_TRY(hipGetLastError());
+    t.stop();
+    return PGPU_OK;
+  };
+  RC_TRY(launch(0, sl_at, st_at, S));
+  if (S > 1) RC_TRY(launch(tab_bytes, fsl_at, fst_at, 1));
+  for (const auto& kv : pair_of) RC_TRY(lanes_order(kv.second, lane, false));
+  *out = o.release();
+  return PGPU_OK;
+}
+
 // ---- encrypted segmented prefix sum (hensel_segscan.hpp; policy.hpp: segscan_*) ----
 int pgpu_ct_segment_scan_plan(int key_bits, size_t rows, size_t seg_len, int* chunk, int* levels, size_t* products) {
   if (key_bits < 1 || rows == 0 || seg_len == 0)

@@ -1,5 +1,5 @@
-// ipcl::ext::matVec / dot / sparseMatVec -- linear maps on encrypted vectors (include/ipcl/ext/linear.hpp): one
-// pgpu_batch_ct_matvec / pgpu_batch_ct_spmv call on resident batches.  The reference composes such a map from CipherText::operator*
+// ipcl::ext::matVec / dot / sparseMatVec / weightedSum / sum -- linear maps on encrypted vectors (include/ipcl/ext/linear.hpp): one
+// pgpu_batch_ct_matvec / pgpu_batch_ct_spmv / pgpu_batch_ct_weighted_sum call on resident batches.  The reference composes such a map from CipherText::operator*
 // (ciphertext.cpp:83-106) and operator+ (ciphertext.cpp:35-72) term by term.
 #include "ipcl/ext/linear.hpp"
 
@@ -43,8 +43,52 @@ CipherText CipherText::sparseLinearMap(const std::vector<uint64_t>& row_ptr, con
   return CipherText(m_pk, detail::DeviceBatch::adopt(o));
 }
 
+CipherText CipherText::weightedSumMap(const std::vector<CipherText>& xs, const PlainText* w) {
+  ERROR_CHECK(!xs.empty(), "weightedSum error: no CipherText");
+  ERROR_CHECK(xs[0].m_size > 0, "weightedSum error: empty CipherText");
+  ERROR_CHECK(!w || w->getSize() == xs.size(), "weightedSum error: Size mismatch! (one weight per CipherText)");
+  const std::shared_ptr<PublicKey>& pk = xs[0].m_pk;
+  for (const CipherText& x : xs) {
+    ERROR_CHECK(x.m_size == xs[0].m_size, "weightedSum error: Size mismatch!");
+    ERROR_CHECK(*(x.m_pk->getN()) == *(pk->getN()), "weightedSum error: 2 different public keys detected!");
+  }
+  const BigNumber& nsq = *(pk->getNSQ());
+  const int W = detail::words_for_bits(nsq.BitSize());
+  // the weights as host words: the schedule is built from them, the device never reads them
+  std::vector<uint64_t> words;
+  int ww = 0;
+  if (w) {
+    const std::vector<BigNumber> a = w->getTexts();
+    int bits = 1;
+    for (const auto& e : a) {
+      ERROR_CHECK(!e.isNegative(), "weightedSum error: negative plaintext");
+      bits = std::max(bits, e.BitSize());
+    }
+    ww = detail::words_for_bits(bits);
+    words.assign(a.size() * (size_t)ww, 0);
+    std::vector<Ipp32u> v;
+    for (size_t k = 0; k < a.size(); ++k) {
+      v.clear();
+      a[k].num2vec(v);
+      for (size_t j = 0; j < v.size() && j < (size_t)2 * ww; ++j) words[k * (size_t)ww + j / 2] |= (uint64_t)v[j] << (32 * (j & 1));
+    }
+  }
+  std::vector<std::shared_ptr<detail::DeviceBatch>> keep;      // device-resident operands are used in place
+  std::vector<const pgpu_batch*> hs;
+  for (const CipherText& x : xs) {
+    keep.push_back(x.deviceBatch(W, &nsq));
+    hs.push_back(keep.back()->h);
+  }
+  pgpu_batch* o = nullptr;
+  IPCL_GPU_CHECK(pgpu_batch_ct_weighted_sum(pk->device()->h, hs.data(), hs.size(), w ? words.data() : nullptr, ww, &o),
+                 "weightedSum");
+  return CipherText(pk, detail::DeviceBatch::adopt(o));
+}
+
 namespace ext {
 
+CipherText weightedSum(const std::vector<CipherText>& xs, const PlainText& w) { return CipherText::weightedSumMap(xs, &w); }
+CipherText sum(const std::vector<CipherText>& xs) { return CipherText::weightedSumMap(xs, nullptr); }
 CipherText matVec(const PlainText& w, std::size_t rows, const CipherText& x) { return x.linearMap(w, rows); }
 CipherText dot(const PlainText& w, const CipherText& x) { return matVec(w, 1, x); }
 CipherText sparseMatVec(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx, const PlainText& w,

@@ -1,5 +1,5 @@
 // pailliercryptolib_amd -- instantiations of the split-form CRT-decrypt exponentiation (hensel.hpp), split over
-// PGPU_PART = 0..55 so that they compile in parallel (53-55: the encrypted sparse matrix-vector product; 38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 45-47: the encrypted segmented prefix sum; 48-51: the encrypted slot packing; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
+// PGPU_PART = 0..59 so that they compile in parallel (56-59: the encrypted weighted sum of K resident batches; 53-55: the encrypted sparse matrix-vector product; 38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 45-47: the encrypted segmented prefix sum; 48-51: the encrypted slot packing; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
 // the two-wavefronts-per-SIMD build of the (2,19) decrypt form; 11-13: element-wise operations on pair rows).
 #include "hensel_seq.hpp"
 #include "launch.hpp"
@@ -30,9 +30,12 @@
 #if defined(PGPU_PART) && PGPU_PART >= 53 && PGPU_PART <= 55
 #include "hensel_spmv.hpp"      // the encrypted sparse matrix-vector product: one multi-exponentiation per chain of a CSR row
 #endif
+#if defined(PGPU_PART) && PGPU_PART >= 56 && PGPU_PART <= 59
+#include "hensel_wsum.hpp"      // the encrypted weighted sum of K resident batches: one launch-uniform bit-serial schedule
+#endif
 
 #ifndef PGPU_PART
-#error "compile with -DPGPU_PART=0..55 (15 and 30 are retired)"
+#error "compile with -DPGPU_PART=0..59 (15 and 30 are retired)"
 #endif
 
 namespace pgpu {
@@ -576,6 +579,30 @@ bool PGPU_PK_NAME(int G, int K, const PackArgs& a, unsigned blocks, hipStream_t 
 bool PGPU_SP_NAME(int G, int K, const SpmvArgs& a, unsigned blocks, hipStream_t s) {
   if (G != PGPU_SP_G || K != PGPU_SP_K) return false;
   hipLaunchKernelGGL((spmv_kernel<PGPU_SP_G, PGPU_SP_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
+  return true;
+}
+#elif PGPU_PART >= 56 && PGPU_PART <= 59
+// the encrypted weighted sum of K resident batches (hensel_wsum.hpp): one geometry per part; 59 is the 2048-bit class on 8 lanes
+#if PGPU_PART == 56
+#define PGPU_WS_G 2
+#define PGPU_WS_K 19
+#define PGPU_WS_NAME launch_wsum_part56
+#elif PGPU_PART == 57
+#define PGPU_WS_G 4
+#define PGPU_WS_K 18
+#define PGPU_WS_NAME launch_wsum_part57
+#elif PGPU_PART == 58
+#define PGPU_WS_G 8
+#define PGPU_WS_K 14
+#define PGPU_WS_NAME launch_wsum_part58
+#else
+#define PGPU_WS_G 8
+#define PGPU_WS_K 9
+#define PGPU_WS_NAME launch_wsum_part59
+#endif
+bool PGPU_WS_NAME(int G, int K, const WsumArgs& a, unsigned blocks, unsigned blocks_y, hipStream_t s) {
+  if (G != PGPU_WS_G || K != PGPU_WS_K) return false;
+  hipLaunchKernelGGL((wsum_kernel<PGPU_WS_G, PGPU_WS_K>), dim3(blocks, blocks_y), dim3(kWGThreads), 0, s, a);
   return true;
 }
 #else

@@ -387,6 +387,38 @@ struct PackArgs {
   uint32_t* out;             // [rows][2*L2], never the same memory as src
 };
 
+// Encrypted weighted sum of K resident batches on pair rows (hensel_wsum.hpp): out[i] = prod_k rows[k][i]^(a_k), the
+// weights a_k the same for every element of the launch.  The host (policy.hpp: wsum_plan) turns them into a bit-serial
+// schedule: per slice of the terms a list of steps, each either "square the accumulator" (op == kWsumSqr) or "multiply
+// by the row of term op".  `next` of a MUL step names the term of the MUL after it (kWsumNone after the last one: the row
+// of one is read and never used), so the kernel loads that row under the running product and never scans ahead.  The
+// accumulator of a slice starts as the row of term `first` (kWsumNone: the row of one -- every weight is zero), the first
+// staged operand is the row of term `first_mul`.  Slice blockIdx.y writes its rows to its own dst.  The fold of a sliced
+// call is the same kernel: rows names the partial regions, the step list is all MUL.
+struct WsumStep {
+  uint32_t op;               // kWsumSqr, or the term of a MUL
+  uint32_t next;             // MUL steps: the term of the next MUL step of the slice, or kWsumNone
+};
+constexpr uint32_t kWsumSqr = 0xFFFFFFFFu;
+constexpr uint32_t kWsumNone = 0xFFFFFFFEu;
+struct WsumSlice {
+  uint32_t* dst;             // [count][2*L2] where the slice stores (host plan: unset, the call fills it in)
+  uint64_t step_begin;       // first step of the slice in WsumArgs::steps
+  uint32_t n_steps;          // below 2^31
+  uint32_t first;            // term the accumulator is loaded from, or kWsumNone
+  uint32_t first_mul;        // term of the first MUL step, or kWsumNone
+  uint32_t term_begin;       // the slice covers the terms term_begin .. term_end - 1 (host side; the kernel does not read them)
+  uint32_t term_end;
+  uint32_t pad_;
+};
+struct WsumArgs {
+  HenselPubDev ctx;
+  const uint32_t* const* rows;   // [n_terms] base of every operand batch, [count][2*L2] pair rows each; every entry addressable
+  const WsumSlice* slices;       // [gridDim.y]
+  const WsumStep* steps;
+  size_t count;                  // >= 1
+};
+
 struct FixedBaseArgs {
   ModCtxDev ctx;         // modulus n^2 (nr set)
   const uint32_t* table; // [nwin][2^w][L]

@@ -366,6 +366,19 @@ inline bool launch_spmv(int G, int K, const SpmvArgs& a, unsigned blocks, hipStr
          launch_spmv_part55(G, K, a, blocks, s);
 }
 
+// The encrypted weighted sum of K resident batches (hensel_wsum.hpp; k_hensel.hip parts 56-59): one bit-serial chain per
+// element over a launch-uniform step list, in the geometries matvec_has lists, and -- part 59 -- with the 72 limbs of a
+// 2048-bit key's half on 8 lanes instead of 4, as the segmented sum and the packing have it.  blocks_y: slices.
+inline bool wsum_wide_has(int G, int K) { return G == 8 && K == 9; }
+bool launch_wsum_part56(int G, int K, const WsumArgs& a, unsigned blocks, unsigned blocks_y, hipStream_t s);
+bool launch_wsum_part57(int G, int K, const WsumArgs& a, unsigned blocks, unsigned blocks_y, hipStream_t s);
+bool launch_wsum_part58(int G, int K, const WsumArgs& a, unsigned blocks, unsigned blocks_y, hipStream_t s);
+bool launch_wsum_part59(int G, int K, const WsumArgs& a, unsigned blocks, unsigned blocks_y, hipStream_t s);
+inline bool launch_wsum(int G, int K, const WsumArgs& a, unsigned blocks, unsigned blocks_y, hipStream_t s) {
+  return launch_wsum_part56(G, K, a, blocks, blocks_y, s) || launch_wsum_part57(G, K, a, blocks, blocks_y, s) ||
+         launch_wsum_part58(G, K, a, blocks, blocks_y, s) || launch_wsum_part59(G, K, a, blocks, blocks_y, s);
+}
+
 // DJN encrypt to pair rows in the same form (k_hensel.hip parts 20, 21, 28): (4,18) 2048-bit keys, (8,14) 3072, (2,19) 1024
 inline bool hensel_fb_encrypt_seq_has(int G, int K) { return (G == 4 && K == 18) || (G == 8 && K == 14) || (G == 2 && K == 19); }
 bool launch_hensel_fb_encrypt_seq_part28(int G, int K, const HenselFbArgs& a, unsigned blocks, hipStream_t s);

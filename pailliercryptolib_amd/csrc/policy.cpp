@@ -540,5 +540,105 @@ bool pack_geometry(int key_bits, size_t rows, int* G, int* K) {
   return true;
 }
 
+
+// ---- encrypted weighted sum of K resident batches ----
+size_t wsum_slices(int G, size_t count, size_t n_terms, bool unit_weights) {
+  if (count == 0 || n_terms == 0) return 1;
+  const long forced = env_now("PGPU_WSUM_SLICES");
+  if (forced > 0) return std::min((size_t)forced, n_terms);
+  const size_t ipw = 64 / (size_t)G;
+  const size_t row_waves = (count + ipw - 1) / ipw;              // wavefronts of one slice
+  const size_t fill = (kSimds + row_waves - 1) / row_waves;      // slices that put a wavefront on every SIMD
+  const size_t cap = std::max<size_t>(1, n_terms / (unit_weights ? 2 : kMatvecMinSliceCols));
+  return std::max<size_t>(1, std::min(std::min(fill, cap), n_terms));
+}
+bool wsum_wide_pays(int wide_G, size_t chains) {
+  const char* e = std::getenv("PGPU_WSUM_WIDE");     // (unset is not 0 here: both values force)
+  if (e && (e[0] == '0' || e[0] == '1') && !e[1]) return e[0] == '1';
+  return segsum_wide_pays(wide_G, chains);
+}
+bool wsum_geometry(int key_bits, size_t chains, int* G, int* K) {
+  int g = 0, k = 0;
+  if (!matvec_geometry(key_bits, &g, &k)) return false;
+  if (k % 2 == 0 && pgpu::wsum_wide_has(2 * g, k / 2) && wsum_wide_pays(2 * g, chains)) {
+    g *= 2;
+    k /= 2;
+  }
+  if (G) *G = g;
+  if (K) *K = k;
+  return true;
+}
+bool wsum_plan(const uint64_t* weights, int w_words, size_t n_terms, size_t S, WsumPlan* plan) {
+  constexpr size_t kMax = (size_t)1 << 31;
+  if (n_terms == 0 || n_terms > kWsumMaxTerms || S == 0 || (weights && w_words < 1)) return false;
+  S = std::min(S, n_terms);
+  const size_t ww = weights ? (size_t)w_words : 1;
+  static const uint64_t kOne = 1;
+  auto word = [&](size_t k, size_t j) -> uint64_t { return weights ? weights[k * ww + j] : kOne; };
+  // bit length and popcount of every weight; then the step count of every slice, before anything is written
+  std::vector<size_t> len(n_terms, 0), pop(n_terms, 0);
+  for (size_t k = 0; k < n_terms; ++k)
+    for (size_t j = 0; j < ww; ++j) {
+      const uint64_t v = word(k, j);
+      if (!v) continue;
+      len[k] = 64 * j + (size_t)(64 - __builtin_clzll(v));
+      pop[k] += (size_t)__builtin_popcountll(v);
+    }
+  struct Cut { size_t lo, hi, top, pops; };
+  std::vector<Cut> cuts;
+  for (size_t s = 0; s < S; ++s) {
+    Cut c{s * n_terms / S, (s + 1) * n_terms / S, 0, 0};
+    for (size_t k = c.lo; k < c.hi; ++k) {
+      c.top = std::max(c.top, len[k]);
+      c.pops += pop[k];
+    }
+    if (c.pops == 0) continue;                         // (every weight of the slice is zero: dropped)
+    if (c.top - 1 + c.pops - 1 >= kMax) return false;
+    cuts.push_back(c);
+  }
+  WsumPlan p;
+  if (cuts.empty()) {
+    p.all_zero = true;
+    WsumSlice sl{};
+    sl.first = sl.first_mul = kWsumNone;
+    sl.term_end = (uint32_t)n_terms;
+    p.slices.push_back(sl);
+    *plan = std::move(p);
+    return true;
+  }
+  for (const Cut& c : cuts) {
+    WsumSlice sl{};
+    sl.step_begin = p.steps.size();
+    sl.first = sl.first_mul = kWsumNone;
+    sl.term_begin = (uint32_t)c.lo;
+    sl.term_end = (uint32_t)c.hi;
+    size_t last_mul = (size_t)-1;                      // the MUL step whose `next` the coming MUL fills in
+    for (size_t bit = c.top; bit-- > 0;) {
+      if (bit != c.top - 1) {
+        p.steps.push_back({kWsumSqr, kWsumNone});
+        ++p.squarings;
+      }
+      for (size_t k = c.lo; k < c.hi; ++k) {
+        if (!((word(k, bit >> 6) >> (bit & 63)) & 1)) continue;
+        if (sl.first == kWsumNone) {                   // the load of the accumulator: no step
+          sl.first = (uint32_t)k;
+          continue;
+        }
+        if (last_mul == (size_t)-1) sl.first_mul = (uint32_t)k;
+        else p.steps[last_mul].next = (uint32_t)k;
+        last_mul = p.steps.size();
+        p.steps.push_back({(uint32_t)k, kWsumNone});
+        ++p.muls;
+      }
+    }
+    sl.n_steps = (uint32_t)(p.steps.size() - sl.step_begin);
+    p.longest = std::max(p.longest, (size_t)sl.n_steps);
+    p.slices.push_back(sl);
+  }
+  p.products = p.squarings + p.muls + (p.slices.size() - 1);
+  *plan = std::move(p);
+  return true;
+}
+
 }  // namespace policy
 }  // namespace pgpu

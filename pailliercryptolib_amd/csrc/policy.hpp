@@ -298,6 +298,47 @@ bool pack_wide_pays(int wide_G, size_t rows);
 // the (G, K) form a call over `rows` output rows launches for keys of key_bits; false: no pair rows for such keys
 bool pack_geometry(int key_bits, size_t rows, int* G, int* K);
 
+
+// ---- the encrypted weighted sum of K resident batches (hensel_wsum.hpp; pgpu_batch_ct_weighted_sum,
+//      pgpu_ct_weighted_sum_plan) ----
+// out[i] = prod_k X_k[i]^(a_k), one plaintext weight per BATCH: the weights are the same for every element, so the
+// schedule is built here, once, and is uniform for the launch.
+// 1. the schedule of one slice of the terms: from the highest set bit over the slice's weights down to bit 0 one SQR step
+//    per bit (none before the top bit), after it one MUL k step for every term k of the slice whose weight has that bit
+//    set, in term order.  The accumulator is LOADED from the first operand (WsumSlice::first), not multiplied into a one:
+//    a slice whose weights are L bits long costs (L - 1) squarings and (sum of popcounts - 1) general products, and its
+//    step list holds exactly that many steps.  A zero weight contributes nothing and its batch is never named.
+// 2. the slices: the terms are cut into S contiguous ranges of floor/ceil(n_terms / S) terms; every slice runs its own
+//    squarings, the partial rows are folded afterwards (one product per further slice).  S is the matvec's rule, CARRIED
+//    OVER from section 11, not fitted to this kernel: the smallest S that puts a wavefront on every SIMD for this count
+//    and G, while a slice keeps at least kMatvecMinSliceCols terms (the squarings a slice repeats stay a bounded share of
+//    its products); 1 <= S <= n_terms.  Without weights (all ones) there are no squarings and a cut costs one fold product
+//    only: the cap is then "at least 2 terms per slice".  Slices whose weights are all zero are dropped; when every
+//    weight is zero one slice remains whose `first` is kWsumNone (the ciphertext 1, no product).
+//    PGPU_WSUM_SLICES=s forces S (clamped to n_terms; read at every call: the tests reach every path with it).
+constexpr size_t kWsumMaxTerms = 65535;
+size_t wsum_slices(int G, size_t count, size_t n_terms, bool unit_weights);
+// 3. the form: (2,19), (4,18), (8,14) by pair_form_for_bits; a 2048-bit key has the (8,9) form beside (4,18) -- the same
+//    rows, half the serial time per product, half the chains per wavefront -- for launches of `chains` = count * slices
+//    chains that put at most one wavefront on a SIMD even then (segsum_wide_pays' rule, as pack_wide_pays carries it).
+//    PGPU_WSUM_WIDE=0 / 1 forces the base / the wide form (read at every call).
+bool wsum_wide_pays(int wide_G, size_t chains);
+bool wsum_geometry(int key_bits, size_t chains, int* G, int* K);
+// 4. the plan.  weights: [n_terms][w_words] little-endian 64-bit words, or null: every weight is 1.  slices: only the
+//    non-empty ones (dst unset: the call fills it in), steps: their lists one after the other.  products is per ELEMENT:
+//    the steps of all slices plus (slices - 1) for the fold -- exact, the idle groups of a last wavefront not counted.
+//    false: n_terms == 0 or beyond kWsumMaxTerms, S == 0, w_words < 1 with weights, or a slice of 2^31 steps or more
+//    (nothing is written then).
+struct WsumPlan {
+  std::vector<WsumSlice> slices;      // >= 1 entry
+  std::vector<WsumStep> steps;
+  size_t longest = 0;                 // steps of the longest slice
+  size_t squarings = 0, muls = 0;     // over all slices, the fold not included
+  size_t products = 0;                // squarings + muls + (slices.size() - 1)
+  bool all_zero = false;              // every weight is zero: one slice, first == kWsumNone
+};
+bool wsum_plan(const uint64_t* weights, int w_words, size_t n_terms, size_t S, WsumPlan* plan);
+
 }  // namespace policy
 }  // namespace pgpu
 

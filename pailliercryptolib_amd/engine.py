@@ -217,6 +217,46 @@ class PublicKey:
                     L.pgpu_batch_destroy(h)
         return limbs_to_ints(out)
 
+    def weighted_sum(self, xs, w=None):
+        """Encrypted weighted sum across K batches: xs a list of K lists of ciphertexts (ints modulo n^2), all of one
+        length, w one non-negative int per LIST (None: all ones, the plain sum) -> the list of ciphertexts
+        prod_k xs[k][i]^w[k] mod n^2, i.e. encryptions of sum_k w[k] * m_k[i] mod n -- a federated average over K
+        clients' vectors.  A zero weight contributes 1; all weights zero give 1 everywhere.  One
+        pgpu_batch_ct_weighted_sum call on resident batches (one bit-serial schedule shared by all elements); there is
+        no element-wise fall-back."""
+        K = len(xs)
+        if K == 0 or len(xs[0]) == 0 or any(len(x) != len(xs[0]) for x in xs):
+            raise RuntimeError("weighted sum error: Size mismatch!")
+        wa = None
+        if w is not None:
+            flat = [int(v) for v in w]
+            if len(flat) != K:
+                raise RuntimeError("weighted sum error: Size mismatch! (one weight per batch)")
+            if min(flat) < 0:
+                raise RuntimeError("weighted sum error: negative weights have no encoding (pass w mod n)")
+            ew = max(1, (max(v.bit_length() for v in flat) + 63) // 64)
+            wa = ints_to_limbs(flat, ew)
+        L = _capi.lib()
+        W = 2 * self.n_words
+        count = len(xs[0])
+        hs, ho = [], ctypes.c_void_p()
+        try:
+            for x in xs:
+                h = ctypes.c_void_p()
+                xa = ints_to_limbs([int(v) for v in x], W)
+                _capi.check(L.pgpu_batch_upload(_ptr(xa), count, W, W, ctypes.byref(h)))
+                hs.append(h)
+            arr = (ctypes.c_void_p * K)(*[h.value for h in hs])
+            _capi.check(L.pgpu_batch_ct_weighted_sum(self._h, arr, K, _ptr(wa) if wa is not None else None,
+                                                     wa.shape[1] if wa is not None else 0, ctypes.byref(ho)))
+            out = np.empty((count, W), dtype=np.uint64)
+            _capi.check(L.pgpu_batch_download(ho, _ptr(out)))
+        finally:
+            for h in hs + [ho]:
+                if h:
+                    L.pgpu_batch_destroy(h)
+        return limbs_to_ints(out)
+
     def segment_sum(self, x, ids, n_segments):
         """Encrypted segmented sum: x a list of ciphertexts (ints modulo n^2), ids one flat list of segment numbers (one
         group) or a list of such lists (several groupings of the same x); None leaves an element out of that group ->
