@@ -17,6 +17,7 @@
 #include <set>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -2722,7 +2723,8 @@ int pgpu_paillier_decrypt_crt(const pgpu_privkey* key, const uint64_t* c, uint64
   });
 }
 
-#include "capi_batches.inc"   // pgpu_batch_*
+#include "capi_batches.inc"   // pgpu_batch_*: upload / download, encrypt / decrypt, element-wise operations, lanes
+#include "capi_aggregate.inc" // pgpu_batch_ct_matvec / _spmv / _weighted_sum / _segment_sum / _segment_scan / _pack, pgpu_ct_*_plan
 
 // ---- diagnostics of the pool's self-checks and table budget ----
 int pgpu_replication_stats(uint64_t* images_verified, uint64_t* copies_repaired) {

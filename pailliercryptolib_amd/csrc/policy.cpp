@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
+#include <cstring>
 #include <utility>
 
 #include "launch.hpp"
@@ -638,6 +639,59 @@ bool wsum_plan(const uint64_t* weights, int w_words, size_t n_terms, size_t S, W
   p.products = p.squarings + p.muls + (p.slices.size() - 1);
   *plan = std::move(p);
   return true;
+}
+
+
+// ---- plan images ----
+static_assert(sizeof(SegsumChunk) == 16 && sizeof(SegscanChunk) == 16, "descriptors are packed into one image behind a 16-byte boundary");
+size_t PlanImage::add(const void* src, size_t n, size_t align) {
+  const size_t at = (bytes.size() + align - 1) / align * align;
+  bytes.resize(at + n, 0);
+  if (src && n) std::memcpy(bytes.data() + at, src, n);
+  return at;
+}
+
+void segsum_image(const std::vector<uint32_t>& perm, const SegsumPlan& plan, SegsumImage* out) {
+  *out = SegsumImage();
+  if (perm.empty()) out->image.add(nullptr, sizeof(uint32_t));
+  else out->image.add(perm);
+  for (size_t l = 0; l < plan.levels.size(); ++l) {
+    out->level_at.push_back(out->image.add(plan.levels[l].chunks, l == 0 ? 16 : 1));
+    out->region[l & 1] = std::max(out->region[l & 1], plan.levels[l].partial_rows);
+  }
+}
+
+void spmv_image(const uint32_t* col_idx, size_t nnz, const SpmvPlan& plan, SpmvImage* out) {
+  *out = SpmvImage();
+  out->image.add(col_idx, nnz * sizeof(uint32_t));
+  out->chains_at = out->image.add(plan.chains, 16);
+  out->region[0] = plan.partial_rows;
+  for (size_t f = 0; f < plan.fold.levels.size(); ++f) {
+    out->fold_at.push_back(out->image.add(plan.fold.levels[f].chunks));
+    out->region[(f + 1) & 1] = std::max(out->region[(f + 1) & 1], plan.fold.levels[f].partial_rows);
+  }
+}
+
+void segscan_image(const SegscanPlan& plan, SegscanImage* out) {
+  *out = SegscanImage();
+  for (const SegscanLevel& lv : plan.levels) {
+    out->up_at.push_back(out->image.add(lv.up));
+    out->scan_at.push_back(out->image.add(lv.scan));
+    out->totals_at.push_back(out->scratch_rows);
+    out->carry_at.push_back(out->scratch_rows + lv.totals);
+    out->scratch_rows += 2 * lv.totals;
+  }
+}
+
+void wsum_image(const std::vector<const uint32_t*>& tab, const std::vector<const uint32_t*>& ftab, const WsumPlan& plan,
+                const WsumPlan& fold, WsumImage* out) {
+  *out = WsumImage();
+  out->tab_at = out->image.add(tab);
+  out->ftab_at = out->image.add(ftab);
+  out->slices_at = out->image.add(plan.slices);
+  out->fold_slices_at = out->image.add(fold.slices);
+  out->steps_at = out->image.add(plan.steps);
+  out->fold_steps_at = out->image.add(fold.steps);
 }
 
 }  // namespace policy

@@ -339,6 +339,57 @@ struct WsumPlan {
 };
 bool wsum_plan(const uint64_t* weights, int w_words, size_t n_terms, size_t S, WsumPlan* plan);
 
+
+// ---- plan images: what an aggregation call uploads in one copy (capi_aggregate.inc) ----
+// Sections one after the other; add() pads with zero bytes up to a multiple of `align` first and returns the byte offset
+// of the section.  src == null leaves the n bytes zero.
+struct PlanImage {
+  std::vector<char> bytes;
+  size_t add(const void* src, size_t n, size_t align = 1);
+  template <class T>
+  size_t add(const std::vector<T>& v, size_t align = 1) { return add(v.data(), v.size() * sizeof(T), align); }
+  const char* data() const { return bytes.data(); }
+  size_t size() const { return bytes.size(); }
+};
+// The images of the four planned calls, and the rows of device scratch their levels rotate through.  Only the leading
+// index lists (perm, col_idx) are padded, to 16 bytes, so that the 16-byte descriptors behind them stay aligned; every
+// other section is packed.
+//   segment sum   perm (never empty: one zero entry stands in, the kernel reads entry 0 for the groups past their end),
+//                 then the descriptors of every level, at level_at[l].  Partial rows: level l reads what level l - 1
+//                 wrote, so two regions serve all levels in turn -- level l writes region l & 1 of region[l & 1] rows
+struct SegsumImage {
+  PlanImage image;
+  std::vector<size_t> level_at;
+  size_t region[2] = {0, 0};
+};
+void segsum_image(const std::vector<uint32_t>& perm, const SegsumPlan& plan, SegsumImage* out);
+//   spmv          col_idx, the chain descriptors at chains_at, the descriptors of every fold level at fold_at[f].  The
+//                 chains write region 0, fold level f reads region f & 1 and writes the other one
+struct SpmvImage {
+  PlanImage image;
+  size_t chains_at = 0;
+  std::vector<size_t> fold_at;
+  size_t region[2] = {0, 0};
+};
+void spmv_image(const uint32_t* col_idx, size_t nnz, const SpmvPlan& plan, SpmvImage* out);
+//   segment scan  per level the up-sweep descriptors at up_at[l], then the scan descriptors at scan_at[l].  Scratch rows:
+//                 per level its totals at row totals_at[l] and, beside them, the carries the level below makes of them at
+//                 carry_at[l] (the deepest level has neither)
+struct SegscanImage {
+  PlanImage image;
+  std::vector<size_t> up_at, scan_at, totals_at, carry_at;
+  size_t scratch_rows = 0;
+};
+void segscan_image(const SegscanPlan& plan, SegscanImage* out);
+//   weighted sum  the row bases of the terms (tab), of the slices' results (ftab: empty without a fold), the slice
+//                 descriptors of the launch and of the fold, then their step lists
+struct WsumImage {
+  PlanImage image;
+  size_t tab_at = 0, ftab_at = 0, slices_at = 0, fold_slices_at = 0, steps_at = 0, fold_steps_at = 0;
+};
+void wsum_image(const std::vector<const uint32_t*>& tab, const std::vector<const uint32_t*>& ftab, const WsumPlan& plan,
+                const WsumPlan& fold, WsumImage* out);
+
 }  // namespace policy
 }  // namespace pgpu
 

@@ -148,6 +148,30 @@ class PublicKey:
             raise RuntimeError("encrypt: Cannot encrypt empty PlainText")
         return limbs_to_ints(self.encrypt_limbs(ints_to_limbs(m, mw), ints_to_limbs(r, rw)))
 
+    def _resident_call(self, operands, rows, call):
+        """One aggregation call on resident batches: uploads every (ints, words per row) of ``operands``, runs
+        ``call(L, handles, byref(out))`` -- the pgpu_batch_ct_* call, which returns its status -- downloads the
+        rows x 2*n_words result and destroys every handle, whatever happened on the way."""
+        L = _capi.lib()
+        hs, ho = [], ctypes.c_void_p()
+        try:
+            arrays = [ints_to_limbs(vals, words) for vals, words in operands]
+            for a in arrays:
+                h = ctypes.c_void_p()
+                _capi.check(L.pgpu_batch_upload(_ptr(a), a.shape[0], a.shape[1], a.shape[1], ctypes.byref(h)))
+                hs.append(h)
+            _capi.check(call(L, hs, ctypes.byref(ho)))
+            out = np.empty((rows, 2 * self.n_words), dtype=np.uint64)
+            _capi.check(L.pgpu_batch_download(ho, _ptr(out)))
+        finally:
+            for h in hs + [ho]:
+                if h:
+                    L.pgpu_batch_destroy(h)
+        return limbs_to_ints(out)
+
+    def _ct(self, x):
+        return [int(v) for v in x], 2 * self.n_words
+
     def matvec(self, x, w, e_bits=None):
         """Encrypted matrix-vector product: x a list of ciphertexts (ints modulo n^2), w a plaintext matrix (a list of
         rows, or one flat row for a dot product) of non-negative ints -> the list of ciphertexts
@@ -163,21 +187,8 @@ class PublicKey:
         if e_bits is None:
             e_bits = max(1, max(v.bit_length() for v in flat))
         ew = (int(e_bits) + 63) // 64
-        L = _capi.lib()
-        W = 2 * self.n_words
-        hx, hw, ho = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-        try:
-            xa, wa = ints_to_limbs([int(v) for v in x], W), ints_to_limbs(flat, ew)
-            _capi.check(L.pgpu_batch_upload(_ptr(xa), cols, W, W, ctypes.byref(hx)))
-            _capi.check(L.pgpu_batch_upload(_ptr(wa), len(flat), ew, ew, ctypes.byref(hw)))
-            _capi.check(L.pgpu_batch_ct_matvec(self._h, hx, hw, len(rows), int(e_bits), ctypes.byref(ho)))
-            out = np.empty((len(rows), W), dtype=np.uint64)
-            _capi.check(L.pgpu_batch_download(ho, _ptr(out)))
-        finally:
-            for h in (hx, hw, ho):
-                if h:
-                    L.pgpu_batch_destroy(h)
-        return limbs_to_ints(out)
+        return self._resident_call([self._ct(x), (flat, ew)], len(rows), lambda L, h, out:
+                                   L.pgpu_batch_ct_matvec(self._h, h[0], h[1], len(rows), int(e_bits), out))
 
     def spmv(self, x, indptr, indices, w, e_bits=None):
         """Encrypted sparse matrix-vector product: x a list of ciphertexts (ints modulo n^2), the plaintext matrix in CSR
@@ -200,22 +211,9 @@ class PublicKey:
         if e_bits is None:
             e_bits = max(1, max(v.bit_length() for v in flat))
         ew = (int(e_bits) + 63) // 64
-        L = _capi.lib()
-        W = 2 * self.n_words
-        hx, hw, ho = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
-        try:
-            xa, wa = ints_to_limbs([int(v) for v in x], W), ints_to_limbs(flat, ew)
-            rp, ci = np.array(indptr, dtype=np.uint64), np.array(indices, dtype=np.uint32)
-            _capi.check(L.pgpu_batch_upload(_ptr(xa), cols, W, W, ctypes.byref(hx)))
-            _capi.check(L.pgpu_batch_upload(_ptr(wa), len(flat), ew, ew, ctypes.byref(hw)))
-            _capi.check(L.pgpu_batch_ct_spmv(self._h, hx, _ptr(rp), _ptr(ci), hw, rows, int(e_bits), ctypes.byref(ho)))
-            out = np.empty((rows, W), dtype=np.uint64)
-            _capi.check(L.pgpu_batch_download(ho, _ptr(out)))
-        finally:
-            for h in (hx, hw, ho):
-                if h:
-                    L.pgpu_batch_destroy(h)
-        return limbs_to_ints(out)
+        rp, ci = np.array(indptr, dtype=np.uint64), np.array(indices, dtype=np.uint32)
+        return self._resident_call([self._ct(x), (flat, ew)], rows, lambda L, h, out:
+                                   L.pgpu_batch_ct_spmv(self._h, h[0], _ptr(rp), _ptr(ci), h[1], rows, int(e_bits), out))
 
     def weighted_sum(self, xs, w=None):
         """Encrypted weighted sum across K batches: xs a list of K lists of ciphertexts (ints modulo n^2), all of one
@@ -236,26 +234,10 @@ class PublicKey:
                 raise RuntimeError("weighted sum error: negative weights have no encoding (pass w mod n)")
             ew = max(1, (max(v.bit_length() for v in flat) + 63) // 64)
             wa = ints_to_limbs(flat, ew)
-        L = _capi.lib()
-        W = 2 * self.n_words
-        count = len(xs[0])
-        hs, ho = [], ctypes.c_void_p()
-        try:
-            for x in xs:
-                h = ctypes.c_void_p()
-                xa = ints_to_limbs([int(v) for v in x], W)
-                _capi.check(L.pgpu_batch_upload(_ptr(xa), count, W, W, ctypes.byref(h)))
-                hs.append(h)
-            arr = (ctypes.c_void_p * K)(*[h.value for h in hs])
-            _capi.check(L.pgpu_batch_ct_weighted_sum(self._h, arr, K, _ptr(wa) if wa is not None else None,
-                                                     wa.shape[1] if wa is not None else 0, ctypes.byref(ho)))
-            out = np.empty((count, W), dtype=np.uint64)
-            _capi.check(L.pgpu_batch_download(ho, _ptr(out)))
-        finally:
-            for h in hs + [ho]:
-                if h:
-                    L.pgpu_batch_destroy(h)
-        return limbs_to_ints(out)
+        return self._resident_call([self._ct(x) for x in xs], len(xs[0]), lambda L, h, out:
+                                   L.pgpu_batch_ct_weighted_sum(self._h, (ctypes.c_void_p * K)(*[v.value for v in h]), K,
+                                                                _ptr(wa) if wa is not None else None,
+                                                                wa.shape[1] if wa is not None else 0, out))
 
     def segment_sum(self, x, ids, n_segments):
         """Encrypted segmented sum: x a list of ciphertexts (ints modulo n^2), ids one flat list of segment numbers (one
@@ -271,20 +253,8 @@ class PublicKey:
         if flat.min() < 0 or ((flat >= n_segments) & (flat != _capi.SEGMENT_NONE)).any():
             raise RuntimeError("segment sum error: a segment id is not below n_segments")
         flat = flat.astype(np.uint32)
-        L = _capi.lib()
-        W = 2 * self.n_words
-        hx, ho = ctypes.c_void_p(), ctypes.c_void_p()
-        try:
-            xa = ints_to_limbs([int(v) for v in x], W)
-            _capi.check(L.pgpu_batch_upload(_ptr(xa), cols, W, W, ctypes.byref(hx)))
-            _capi.check(L.pgpu_batch_ct_segment_sum(self._h, hx, _ptr(flat), len(groups), n_segments, ctypes.byref(ho)))
-            out = np.empty((len(groups) * n_segments, W), dtype=np.uint64)
-            _capi.check(L.pgpu_batch_download(ho, _ptr(out)))
-        finally:
-            for h in (hx, ho):
-                if h:
-                    L.pgpu_batch_destroy(h)
-        return limbs_to_ints(out)
+        return self._resident_call([self._ct(x)], len(groups) * n_segments, lambda L, h, out:
+                                   L.pgpu_batch_ct_segment_sum(self._h, h[0], _ptr(flat), len(groups), n_segments, out))
 
     def segment_scan(self, x, seg_len, reverse=False):
         """Encrypted segmented prefix sum: x a list of ciphertexts (ints modulo n^2) read as [len(x) // seg_len][seg_len]
@@ -294,20 +264,8 @@ class PublicKey:
         count, seg_len = len(x), int(seg_len)
         if count == 0 or seg_len <= 0 or count % seg_len:
             raise RuntimeError("segment scan error: seg_len must be positive and divide len(x)")
-        L = _capi.lib()
-        W = 2 * self.n_words
-        hx, ho = ctypes.c_void_p(), ctypes.c_void_p()
-        try:
-            xa = ints_to_limbs([int(v) for v in x], W)
-            _capi.check(L.pgpu_batch_upload(_ptr(xa), count, W, W, ctypes.byref(hx)))
-            _capi.check(L.pgpu_batch_ct_segment_scan(self._h, hx, seg_len, _capi.SCAN_REVERSE if reverse else 0, ctypes.byref(ho)))
-            out = np.empty((count, W), dtype=np.uint64)
-            _capi.check(L.pgpu_batch_download(ho, _ptr(out)))
-        finally:
-            for h in (hx, ho):
-                if h:
-                    L.pgpu_batch_destroy(h)
-        return limbs_to_ints(out)
+        return self._resident_call([self._ct(x)], count, lambda L, h, out:
+                                   L.pgpu_batch_ct_segment_scan(self._h, h[0], seg_len, _capi.SCAN_REVERSE if reverse else 0, out))
 
     def pack(self, x, seg_len, slot_bits):
         """Encrypted slot packing: x a list of ciphertexts (ints modulo n^2) read as [len(x) // seg_len][seg_len] -> the
@@ -320,20 +278,8 @@ class PublicKey:
             raise RuntimeError("pack error: seg_len must be positive and divide len(x)")
         if not 1 <= slot_bits <= 1 << 30:
             raise RuntimeError("pack error: slot_bits must be positive")
-        L = _capi.lib()
-        W = 2 * self.n_words
-        hx, ho = ctypes.c_void_p(), ctypes.c_void_p()
-        try:
-            xa = ints_to_limbs([int(v) for v in x], W)
-            _capi.check(L.pgpu_batch_upload(_ptr(xa), count, W, W, ctypes.byref(hx)))
-            _capi.check(L.pgpu_batch_ct_pack(self._h, hx, seg_len, slot_bits, ctypes.byref(ho)))
-            out = np.empty((count // seg_len, W), dtype=np.uint64)
-            _capi.check(L.pgpu_batch_download(ho, _ptr(out)))
-        finally:
-            for h in (hx, ho):
-                if h:
-                    L.pgpu_batch_destroy(h)
-        return limbs_to_ints(out)
+        return self._resident_call([self._ct(x)], count // seg_len, lambda L, h, out:
+                                   L.pgpu_batch_ct_pack(self._h, h[0], seg_len, slot_bits, out))
 
 
 def unpack_slots(ms, seg_len, slot_bits, width_bits=None):

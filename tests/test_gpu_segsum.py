@@ -149,7 +149,9 @@ def test_forced_chunks_reach_every_level(engine, knobs, bits):
 
 def test_plan_image_beyond_the_bounce_buffer(engine, knobs):
     """many groupings of few ciphertexts: the sorted list and the descriptors (over 256 KiB) reach the device through a
-    worker lane's staging buffers instead of the calling thread's bounce buffer"""
+    worker lane's staging buffers instead of the calling thread's bounce buffer.  That choice is written once
+    (csrc/capi_aggregate.inc: upload_plan_image) for the four calls that upload a plan image -- segment sum, spmv, weighted
+    sum, segment scan -- so this case exercises the large path of all of them"""
     c = Case(engine, 1024)
     rng = random.Random(12)
     try:

@@ -75,7 +75,7 @@ def run_wsum_kernel(rows, slices, dst, count, ipw, stats):
 
 
 def weighted_sum_model(planner, xs, weights, S, ipw):
-    """the whole call as capi_batches.inc runs it: the slices' launch, then the fold over the regions, in place"""
+    """the whole call as capi_aggregate.inc runs it: the slices' launch, then the fold over the regions, in place"""
     K, count = len(xs), len(xs[0])
     got = planner(weights, K, S)
     assert got is not None
