@@ -4,6 +4,12 @@
 //   matVec(w, rows, x)   y[i] = sum_j w[i*cols + j] * x[j]   under the encryption, cols = x.getSize():
 //                        Y[i] = prod_j X[j]^w[i][j] mod n^2 -- an encrypted linear layer, a weighted aggregate
 //   dot(w, x)            the rows = 1 case
+//   matMul(w, rows, x, n_vec, transposed = false)
+//                        the same map for n_vec vectors at once, cols = x.getSize() / n_vec: x read as [n_vec][cols] and
+//                        the result as [n_vec][rows], Y[v][i] = prod_j X[v][j]^w[i][j] mod n^2 (Y = X * W^T: a linear layer
+//                        applied to a minibatch); transposed: x read as [cols][n_vec], the result as [rows][n_vec]
+//                        (Y = W * X: a per-class gradient X^T * D).  One pgpu_batch_ct_matmul call: the matVec schedule
+//                        per output, the vectors walked in tiles whose window tables share one block.  n_vec = 1 is matVec.
 //   sparseMatVec(row_ptr, col_idx, w, x)
 //                        the same map with the plaintext matrix in CSR form, rows = row_ptr.size() - 1:
 //                        Y[i] = prod_{ row_ptr[i] <= t < row_ptr[i+1] } X[col_idx[t]]^w[t] mod n^2 -- a neighbourhood
@@ -40,6 +46,7 @@ namespace ext {
 
 CipherText matVec(const PlainText& w, std::size_t rows, const CipherText& x);
 CipherText dot(const PlainText& w, const CipherText& x);
+CipherText matMul(const PlainText& w, std::size_t rows, const CipherText& x, std::size_t n_vec, bool transposed = false);
 CipherText sparseMatVec(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx, const PlainText& w,
                         const CipherText& x);
 CipherText weightedSum(const std::vector<CipherText>& xs, const PlainText& w);

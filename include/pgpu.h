@@ -465,6 +465,42 @@ int pgpu_batch_ct_weighted_sum(const pgpu_pubkey* key, const pgpu_batch* const* 
  * schedule of 2^31 steps or more, a product count beyond size_t.  PGPU_ERR_UNSUPPORTED: no pair rows for keys of key_bits. */
 int pgpu_ct_weighted_sum_plan(int key_bits, size_t count, size_t n_terms, const uint64_t* weights_or_null, int w_words,
                               int* lanes, int* limbs, int* slices, size_t* steps, size_t* products);
+/* Encrypted matrix product (an encrypted linear layer applied to a minibatch, a per-class gradient): x a resident
+ * ciphertext batch of n_vec*cols elements (pair rows, or uploaded plain ciphertext words: converted on the way in), read as
+ * n_vec vectors of cols = pgpu_batch_count(x) / n_vec elements; w a plain uploaded batch of rows*cols exponents, row-major
+ * as in pgpu_batch_ct_matvec, each < 2^e_bits (bits at and above e_bits are ignored):
+ *     flags == 0:               x read as [n_vec][cols], out as [n_vec][rows]
+ *         out[v*rows + i] = prod_j x[v*cols + j]^w[i*cols + j] mod n^2          (Y = X * W^T, the nn.Linear convention)
+ *     PGPU_MATMUL_TRANSPOSED:   x read as [cols][n_vec], out as [rows][n_vec]
+ *         out[i*n_vec + v] = prod_j x[j*n_vec + v]^w[i*cols + j] mod n^2        (Y = W * X)
+ * i.e. Dec(out) = W * Dec(x) mod n for every vector.  With n_vec == 1 both layouts are pgpu_batch_ct_matvec; an all-zero
+ * row of w yields the ciphertext 1; negative weights have no encoding (pass w mod n).  The schedule of an output is the
+ * matvec's; the vectors are walked in tiles -- one tile's window tables are built, used by all rows, and the table block is
+ * reused by the next tile -- so that the tables stay under the cap of the matvec at the window the product count wants,
+ * however many vectors there are ("Encrypted matrix product"; what pgpu_batch_ct_spmv needs n_vec*rows*cols
+ * column numbers and as many weights for, and one table over all of x).  The result is an ordinary resident ciphertext
+ * batch of n_vec*rows elements in pair rows on the lane of x; x is left unchanged.
+ * PGPU_ERR_INVALID_PARAM: null / stale handles, n_vec == 0, rows == 0, count(x) % n_vec != 0, count(w) != rows*cols, w not a
+ * plain uploaded batch, e_bits < 1 or wider than the rows of w, a flag bit other than PGPU_MATMUL_TRANSPOSED, ciphertext
+ * width mismatch, a batch of another key, n_vec*rows beyond size_t.
+ * PGPU_ERR_UNSUPPORTED: keys without pair rows (beyond 3072 bits; PGPU_PAIR_ROWS=0 / PGPU_HENSEL=0), pools of more than one
+ * GPU, and -- SIDE CHANNELS -- the masked table-gather policy: the tables are indexed by digits of the PLAINTEXT matrix w
+ * (never by key material or by anything encrypted), as in pgpu_batch_ct_matvec.
+ * All refusals are decided on the host before any launch and leave *out untouched. */
+#define PGPU_MATMUL_TRANSPOSED 1u
+int pgpu_batch_ct_matmul(const pgpu_pubkey* key, const pgpu_batch* x, const pgpu_batch* w, size_t n_vec, size_t rows,
+                         int e_bits, unsigned flags, pgpu_batch** out);
+/* What a call of this shape would run (host-side query, needs no device): the window width (1..6), the vectors of a tile
+ * (1..n_vec; the call makes ceil(n_vec / tile) passes, the last one over the vectors that remain), the column slices of a
+ * full pass (1..cols; a short last pass has the slices of its own size), the bytes of the table block (tile * cols *
+ * 2^window pair rows) and the pair products of the whole call: per pass over t vectors t*cols*(2^w - 2) for the tables,
+ * t*rows*S*e_bits squarings, t*rows*cols*ceil(e_bits / w) products by table entries, t*rows*(S - 1) for the fold.  Every
+ * pass is a table launch, a multiply launch and ceil(log2 S) fold launches.  The rule is policy.hpp: matmul_plan;
+ * PGPU_MATMUL_WINDOW / PGPU_MATMUL_TILE / PGPU_MATMUL_SLICES force the three values, read at every call.
+ * PGPU_ERR_INVALID_PARAM: a size or e_bits that is not positive, a product count beyond size_t.  PGPU_ERR_UNSUPPORTED: no
+ * pair rows for keys of key_bits. */
+int pgpu_ct_matmul_plan(int key_bits, size_t n_vec, size_t rows, size_t cols, int e_bits,
+                        int* window, int* slices, size_t* tile, size_t* table_bytes, size_t* products);
 
 /* ---- instrumentation used by bench.py (roofline) ----
  * With timing enabled every kernel launch is bracketed by two HIP events recorded on the stream
@@ -481,7 +517,8 @@ typedef enum pgpu_kernel_kind {
   PGPU_KERNEL_SEGSCAN = 7,    /* every launch of pgpu_batch_ct_segment_scan: up-sweeps (segsum_kernel) and scans */
   PGPU_KERNEL_PACK = 8,       /* the launch of pgpu_batch_ct_pack */
   PGPU_KERNEL_SPMV = 9,       /* every launch of pgpu_batch_ct_spmv: table build, multi-exponentiation, fold levels */
-  PGPU_KERNEL_WSUM = 10       /* every launch of pgpu_batch_ct_weighted_sum: the slices' schedules, the fold */
+  PGPU_KERNEL_WSUM = 10,      /* every launch of pgpu_batch_ct_weighted_sum: the slices' schedules, the fold */
+  PGPU_KERNEL_MATMUL = 11     /* every launch of pgpu_batch_ct_matmul: per pass the table build, the multi-exponentiation, the fold */
 } pgpu_kernel_kind;
 int pgpu_set_timing(int enabled);
 int pgpu_timing_collect(int* kinds, double* ms, int max_entries);

@@ -36,6 +36,7 @@ SYMBOLS = [
     "pgpu_encrypt_kernel_form_ex", "pgpu_host_alloc", "pgpu_host_free", "pgpu_host_wait",
     "pgpu_timing_collect_trace",
     "pgpu_batch_ct_matvec", "pgpu_ct_matvec_plan",
+    "pgpu_batch_ct_matmul", "pgpu_ct_matmul_plan",
     "pgpu_batch_ct_segment_sum", "pgpu_ct_segment_sum_plan",
     "pgpu_batch_ct_segment_scan", "pgpu_ct_segment_scan_plan",
     "pgpu_batch_ct_pack", "pgpu_ct_pack_plan",
@@ -176,6 +177,11 @@ def lib():
     L.pgpu_batch_ct_matvec.restype = c_int
     L.pgpu_ct_matvec_plan.argtypes = [c_int, c_size_t, c_size_t, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_size_t)]
     L.pgpu_ct_matvec_plan.restype = c_int
+    L.pgpu_batch_ct_matmul.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_int, ctypes.c_uint, POINTER(c_void_p)]
+    L.pgpu_batch_ct_matmul.restype = c_int
+    L.pgpu_ct_matmul_plan.argtypes = [c_int, c_size_t, c_size_t, c_size_t, c_int, POINTER(c_int), POINTER(c_int),
+                                      POINTER(c_size_t), POINTER(c_size_t), POINTER(c_size_t)]
+    L.pgpu_ct_matmul_plan.restype = c_int
     L.pgpu_batch_ct_segment_sum.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, POINTER(c_void_p)]
     L.pgpu_batch_ct_segment_sum.restype = c_int
     L.pgpu_ct_segment_sum_plan.argtypes = [c_int, c_size_t, c_size_t, c_size_t, POINTER(c_int), POINTER(c_int)]

@@ -1,4 +1,4 @@
-// pailliercryptolib_amd -- the aggregation calls on resident ciphertexts (pgpu_batch_ct_matvec / _spmv / _weighted_sum /
+// pailliercryptolib_amd -- the aggregation calls on resident ciphertexts (pgpu_batch_ct_matvec / _matmul / _spmv / _weighted_sum /
 // _segment_sum / _segment_scan / _pack) and their plan queries (pgpu_ct_*_plan).
 // Part of the translation unit of capi.cpp (included there, in place, after capi_batches.inc, whose bounce buffer the plan
 // upload shares).  Every call is: its own parameter checks, the admission tail, its plan (policy.hpp), the result set-up,
@@ -198,6 +198,134 @@ int pgpu_batch_ct_matvec(const pgpu_pubkey* key, const pgpu_batch* x, const pgpu
     pa.out = h == 1 ? r.o->prow(0) : (uint32_t*)partial.p;
     RC_TRY(pair_op_launch(*r.dev, lf, pa, r.s, PGPU_KERNEL_MATVEC));
     cur = h;
+  }
+  RC_TRY(lanes_order(w, r.x->lane, false));
+  return r.finish(out);
+}
+
+// ---- encrypted matrix product (hensel_matmul.hpp; policy.hpp: matmul_*) ----
+int pgpu_ct_matmul_plan(int key_bits, size_t n_vec, size_t rows, size_t cols, int e_bits,
+                        int* window, int* slices, size_t* tile, size_t* table_bytes, size_t* products) {
+  if (key_bits < 1 || n_vec == 0 || rows == 0 || cols == 0 || e_bits < 1)
+    return fail(PGPU_ERR_INVALID_PARAM, "matmul plan: key_bits, n_vec, rows, cols and e_bits must be positive");
+  int G = 0, K = 0;
+  if (!policy::matvec_geometry(key_bits, &G, &K))
+    return fail(PGPU_ERR_UNSUPPORTED, "matmul: keys of this size have no pair rows (1024- to 3072-bit key classes only)");
+  const size_t row_bytes = (size_t)2 * G * K * sizeof(uint32_t);
+  policy::MatmulPlan plan;
+  policy::matmul_plan(G, n_vec, rows, cols, e_bits, row_bytes, &plan);
+  if (plan.products >= 18446744073709551615.0) return fail(PGPU_ERR_INVALID_PARAM, "matmul plan: the product count overflows");
+  if (window) *window = plan.window;
+  if (slices) *slices = (int)plan.slices;
+  if (tile) *tile = plan.tile;
+  if (table_bytes) *table_bytes = plan.tile * cols * ((size_t)1 << plan.window) * row_bytes;
+  if (products) *products = (size_t)plan.products;
+  return PGPU_OK;
+}
+
+int pgpu_batch_ct_matmul(const pgpu_pubkey* key, const pgpu_batch* x, const pgpu_batch* w, size_t n_vec, size_t rows,
+                         int e_bits, unsigned flags, pgpu_batch** out) {
+  RC_TRY(rt::check_ready());
+  if (!key || !x || !w || !out) return fail(PGPU_ERR_INVALID_PARAM, "null argument");
+  RC_TRY(check_gen(key->gen, "key"));
+  RC_TRY(check_gen(x->gen, "batch"));
+  RC_TRY(check_gen(w->gen, "batch"));
+  if (n_vec == 0 || rows == 0) return fail(PGPU_ERR_INVALID_PARAM, "matmul error: n_vec and rows must be positive");
+  if (x->count == 0 || x->count % n_vec != 0) return fail(PGPU_ERR_INVALID_PARAM, "matmul error: n_vec must divide count(x)");
+  const size_t cols = x->count / n_vec;
+  if (flags & ~PGPU_MATMUL_TRANSPOSED) return fail(PGPU_ERR_INVALID_PARAM, "matmul error: unknown flag bit (PGPU_MATMUL_TRANSPOSED is the only one)");
+  if (x->words != 2 * key->n_words) return fail(PGPU_ERR_INVALID_PARAM, "matmul error: ciphertext width mismatch");
+  if (w->mont || w->pair_l2) return fail(PGPU_ERR_INVALID_PARAM, "matmul error: the matrix must be a plain uploaded batch");
+  if (rows > ~(size_t)0 / cols || w->count != rows * cols)
+    return fail(PGPU_ERR_INVALID_PARAM, "matmul error: Size mismatch! (the matrix must hold rows * count(x) / n_vec values)");
+  if (e_bits < 1 || e_bits > 64 * w->words) return fail(PGPU_ERR_INVALID_PARAM, "matmul error: e_bits outside the rows of the matrix batch");
+  if (rows > ~(size_t)0 / n_vec) return fail(PGPU_ERR_INVALID_PARAM, "matmul error: n_vec * rows overflows");
+  // (pair rows of another key are reported in the words of the conversion, as_pair_batch, as for the matvec)
+  static const AggOp op{"matmul", "vectors", " and this call indexes its window tables by digits of the plaintext matrix; no masked variant exists",
+                        pgpu::matmul_has, "ciphertext batch belongs to a different key"};
+  const pgpu_pubkey::PubForm* pf = nullptr;
+  RC_TRY(agg_admit(op, key, &x, 1, &pf));
+  const int G = pf->H, K = pf->K;
+  const size_t LQ = (size_t)2 * G * K, row_bytes = LQ * sizeof(uint32_t);
+  const bool tr = (flags & PGPU_MATMUL_TRANSPOSED) != 0;
+  policy::MatmulPlan plan;
+  policy::matmul_plan(G, n_vec, rows, cols, e_bits, row_bytes, &plan);
+  const int win = plan.window;
+  const size_t S_max = std::max(plan.slices, plan.last_slices);
+  AggRun r;
+  RC_TRY(r.open(key, pf, x, n_vec * rows));
+  RC_TRY(lanes_order(w, r.x->lane, true));
+  // one table block and one partial block for all passes: the block arena, on the lane's stream.  A pass of the transposed
+  // layout that is not the whole of x -- its vectors are cols runs of t rows, n_vec rows apart -- goes through a staging
+  // block [cols][t], so that the table build walks a contiguous range, and leaves a folded result [rows][t] the same way
+  const bool staged = tr && plan.tile < n_vec;
+  rt::DevMem table, partial, stage;
+  RC_TRY(table.alloc(*r.dev, r.s, plan.tile * cols * ((size_t)1 << win) * row_bytes));
+  if (S_max > 1) RC_TRY(partial.alloc(*r.dev, r.s, S_max * plan.tile * rows * row_bytes));
+  if (staged) RC_TRY(stage.alloc(*r.dev, r.s, plan.tile * cols * row_bytes));
+  for (size_t p = 0; p < plan.passes; ++p) {
+    const size_t v0 = p * plan.tile, t = p + 1 == plan.passes ? plan.last : plan.tile, n_out = t * rows;
+    const size_t S = p + 1 == plan.passes ? plan.last_slices : plan.slices;
+    const uint32_t* xt = tr ? r.x->prow(0) + v0 * LQ : r.x->prow(0) + v0 * cols * LQ;
+    uint32_t* dest = tr ? r.o->prow(0) + v0 * LQ : r.o->prow(0) + v0 * rows * LQ;   // (transposed: row i of the tile at dest + i * n_vec rows)
+    if (staged) {
+      HIP_TRY(hipMemcpy2DAsync(stage.p, t * row_bytes, xt, n_vec * row_bytes, t * row_bytes, cols, hipMemcpyDeviceToDevice, r.s));
+      xt = (const uint32_t*)stage.p;
+    }
+    {
+      // the unchanged table build of the matvec over the tile: T[e][d] = x_e^d
+      pgpu::MatvecArgs ta{};
+      ta.ctx = hensel_pub_view(pf, r.dev->index);
+      ta.x = xt;
+      ta.table = (uint32_t*)table.p;
+      ta.window = win;
+      ta.cols = t * cols;
+      RC_TRY(timed_launch(r, t * cols, G, PGPU_KERNEL_MATMUL, "matmul", [&](unsigned blocks) { return pgpu::launch_matvec_table(G, K, ta, blocks, r.s); }));
+    }
+    pgpu::MatmulArgs a{};
+    a.ctx = hensel_pub_view(pf, r.dev->index);
+    a.table = (const uint32_t*)table.p;
+    a.w = w->ptr(0);
+    a.w_stride = (size_t)w->words;
+    a.w_words = w->words;
+    a.e_bits = e_bits;
+    a.window = win;
+    a.slices = (int)S;
+    a.n_out = n_out;
+    a.rows = rows;
+    a.cols = cols;
+    a.t_vec_stride = tr ? 1 : cols;
+    a.t_col_stride = tr ? t : 1;
+    if (S > 1) {          // partial products [S][t][rows], transposed [S][rows][t]
+      a.out = (uint32_t*)partial.p;
+      a.o_slice_stride = n_out;
+      a.o_vec_stride = tr ? 1 : rows;
+      a.o_row_stride = tr ? t : 1;
+    } else {              // straight into the result batch
+      a.out = dest;
+      a.o_slice_stride = 0;
+      a.o_vec_stride = tr ? 1 : rows;
+      a.o_row_stride = tr ? n_vec : 1;
+    }
+    RC_TRY(timed_launch(r, n_out, G, PGPU_KERNEL_MATMUL, "matmul", [&](unsigned blocks) { return pgpu::launch_matmul(G, K, a, blocks, r.s); }, S));
+    // fold the S partial products of every output as the matvec does: ceil(log2 S) element-wise pair products over the
+    // slices, in place, the last one into the result batch where the pass's outputs are contiguous there
+    for (size_t cur = S; cur > 1;) {
+      const size_t h = (cur + 1) / 2;
+      pgpu::PairOpsArgs pa{};
+      pa.count = (cur - h) * n_out;
+      const pgpu_pubkey::PubForm* lf = pair_op_form(key, pf, pa.count);
+      pa.ctx = hensel_pub_view(lf, r.dev->index);
+      pa.op = pgpu::PO_MUL;
+      pa.a = (const uint32_t*)partial.p;
+      pa.b = (const uint32_t*)partial.p + h * n_out * LQ;
+      pa.b_stride = LQ;
+      pa.out = h == 1 && !staged ? dest : (uint32_t*)partial.p;
+      RC_TRY(pair_op_launch(*r.dev, lf, pa, r.s, PGPU_KERNEL_MATMUL));
+      cur = h;
+    }
+    if (S > 1 && staged)
+      HIP_TRY(hipMemcpy2DAsync(dest, n_vec * row_bytes, partial.p, t * row_bytes, t * row_bytes, rows, hipMemcpyDeviceToDevice, r.s));
   }
   RC_TRY(lanes_order(w, r.x->lane, false));
   return r.finish(out);

@@ -1,5 +1,5 @@
-// ipcl::ext::matVec / dot / sparseMatVec / weightedSum / sum -- linear maps on encrypted vectors (include/ipcl/ext/linear.hpp): one
-// pgpu_batch_ct_matvec / pgpu_batch_ct_spmv / pgpu_batch_ct_weighted_sum call on resident batches.  The reference composes such a map from CipherText::operator*
+// ipcl::ext::matVec / dot / matMul / sparseMatVec / weightedSum / sum -- linear maps on encrypted vectors (include/ipcl/ext/linear.hpp): one
+// pgpu_batch_ct_matvec / pgpu_batch_ct_matmul / pgpu_batch_ct_spmv / pgpu_batch_ct_weighted_sum call on resident batches.  The reference composes such a map from CipherText::operator*
 // (ciphertext.cpp:83-106) and operator+ (ciphertext.cpp:35-72) term by term.
 #include "ipcl/ext/linear.hpp"
 
@@ -21,6 +21,25 @@ CipherText CipherText::linearMap(const PlainText& w, std::size_t rows) const {
   auto dx = deviceBatch(W, &nsq), dw = w.deviceBatch(ew);
   pgpu_batch* o = nullptr;
   IPCL_GPU_CHECK(pgpu_batch_ct_matvec(m_pk->device()->h, dx->h, dw->h, rows, ebits, &o), "matVec");
+  return CipherText(m_pk, detail::DeviceBatch::adopt(o));
+}
+
+CipherText CipherText::linearMapBatch(const PlainText& w, std::size_t rows, std::size_t n_vec, bool transposed) const {
+  ERROR_CHECK(m_size > 0, "matMul error: empty CipherText");
+  ERROR_CHECK(n_vec > 0 && m_size % n_vec == 0, "matMul error: Size mismatch! (n_vec must divide the CipherText)");
+  const std::size_t cols = m_size / n_vec;
+  ERROR_CHECK(rows > 0 && w.getSize() / rows == cols && w.getSize() % rows == 0, "matMul error: Size mismatch!");
+  const BigNumber& nsq = *(m_pk->getNSQ());
+  const int W = detail::words_for_bits(nsq.BitSize());
+  if (!w.isDeviceResident())
+    for (const auto& e : w.m_texts) ERROR_CHECK(!e.isNegative(), "matMul error: negative plaintext");
+  const int ebits = std::max(1, w.maxBitsHint());
+  const int ew = w.isDeviceResident() ? w.m_dev->words : detail::words_for_bits(ebits);
+  auto dx = deviceBatch(W, &nsq), dw = w.deviceBatch(ew);
+  pgpu_batch* o = nullptr;
+  IPCL_GPU_CHECK(pgpu_batch_ct_matmul(m_pk->device()->h, dx->h, dw->h, n_vec, rows, ebits,
+                                      transposed ? PGPU_MATMUL_TRANSPOSED : 0u, &o),
+                 "matMul");
   return CipherText(m_pk, detail::DeviceBatch::adopt(o));
 }
 
@@ -91,6 +110,9 @@ CipherText weightedSum(const std::vector<CipherText>& xs, const PlainText& w) { 
 CipherText sum(const std::vector<CipherText>& xs) { return CipherText::weightedSumMap(xs, nullptr); }
 CipherText matVec(const PlainText& w, std::size_t rows, const CipherText& x) { return x.linearMap(w, rows); }
 CipherText dot(const PlainText& w, const CipherText& x) { return matVec(w, 1, x); }
+CipherText matMul(const PlainText& w, std::size_t rows, const CipherText& x, std::size_t n_vec, bool transposed) {
+  return x.linearMapBatch(w, rows, n_vec, transposed);
+}
 CipherText sparseMatVec(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx, const PlainText& w,
                         const CipherText& x) {
   return x.sparseLinearMap(row_ptr, col_idx, w);

@@ -1,5 +1,5 @@
 // pailliercryptolib_amd -- instantiations of the split-form CRT-decrypt exponentiation (hensel.hpp), split over
-// PGPU_PART = 0..59 so that they compile in parallel (56-59: the encrypted weighted sum of K resident batches; 53-55: the encrypted sparse matrix-vector product; 38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 45-47: the encrypted segmented prefix sum; 48-51: the encrypted slot packing; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
+// PGPU_PART = 0..62 so that they compile in parallel (60-62: the encrypted matrix product; 56-59: the encrypted weighted sum of K resident batches; 53-55: the encrypted sparse matrix-vector product; 38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 45-47: the encrypted segmented prefix sum; 48-51: the encrypted slot packing; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
 // the two-wavefronts-per-SIMD build of the (2,19) decrypt form; 11-13: element-wise operations on pair rows).
 #include "hensel_seq.hpp"
 #include "launch.hpp"
@@ -33,9 +33,12 @@
 #if defined(PGPU_PART) && PGPU_PART >= 56 && PGPU_PART <= 59
 #include "hensel_wsum.hpp"      // the encrypted weighted sum of K resident batches: one launch-uniform bit-serial schedule
 #endif
+#if defined(PGPU_PART) && PGPU_PART >= 60 && PGPU_PART <= 62
+#include "hensel_matmul.hpp"    // the encrypted matrix product: the matvec's schedule over a tile of vectors
+#endif
 
 #ifndef PGPU_PART
-#error "compile with -DPGPU_PART=0..59 (15 and 30 are retired)"
+#error "compile with -DPGPU_PART=0..62 (15 and 30 are retired)"
 #endif
 
 namespace pgpu {
@@ -603,6 +606,26 @@ bool PGPU_SP_NAME(int G, int K, const SpmvArgs& a, unsigned blocks, hipStream_t 
 bool PGPU_WS_NAME(int G, int K, const WsumArgs& a, unsigned blocks, unsigned blocks_y, hipStream_t s) {
   if (G != PGPU_WS_G || K != PGPU_WS_K) return false;
   hipLaunchKernelGGL((wsum_kernel<PGPU_WS_G, PGPU_WS_K>), dim3(blocks, blocks_y), dim3(kWGThreads), 0, s, a);
+  return true;
+}
+#elif PGPU_PART >= 60 && PGPU_PART <= 62
+// the encrypted matrix product (hensel_matmul.hpp): one geometry per part
+#if PGPU_PART == 60
+#define PGPU_MM_G 2
+#define PGPU_MM_K 19
+#define PGPU_MM_NAME launch_matmul_part60
+#elif PGPU_PART == 61
+#define PGPU_MM_G 4
+#define PGPU_MM_K 18
+#define PGPU_MM_NAME launch_matmul_part61
+#else
+#define PGPU_MM_G 8
+#define PGPU_MM_K 14
+#define PGPU_MM_NAME launch_matmul_part62
+#endif
+bool PGPU_MM_NAME(int G, int K, const MatmulArgs& a, unsigned blocks, hipStream_t s) {
+  if (G != PGPU_MM_G || K != PGPU_MM_K) return false;
+  hipLaunchKernelGGL((matmul_kernel<PGPU_MM_G, PGPU_MM_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
   return true;
 }
 #else

@@ -419,6 +419,28 @@ struct WsumArgs {
   size_t count;                  // >= 1
 };
 
+// Encrypted matrix product on pair rows (hensel_matmul.hpp): one pass over a TILE of vectors,
+//     out(v, i) = prod_j x(v, j)^w[i][j],   v a vector of the tile, i < rows, j < cols.
+// The table is matvec_table_kernel's, built from MatvecArgs over the tile's elements of x: element (v, j) is table row
+// v * t_vec_stride + j * t_col_stride.  Output (v, i) of column slice s is row s * o_slice_stride + v * o_vec_stride +
+// i * o_row_stride of `out` (the result batch, or the partial block the fold reads).  The host keeps every such row
+// inside the table and inside `out`.
+struct MatmulArgs {
+  HenselPubDev ctx;
+  const uint32_t* table;     // [vectors of the tile * cols][2^window][2*L2] T[e][d] = x_e^d
+  const uint64_t* w;         // [rows*cols][w_stride] the plaintext matrix, row-major, each value < 2^e_bits
+  size_t w_stride;
+  int w_words;               // valid words per value
+  int e_bits;                // >= 1
+  int window;                // 1..6
+  int slices;                // 1..cols: column ranges with a partial product each
+  size_t n_out;              // vectors of the tile * rows, >= 1: outputs are numbered flat, o = v * rows + i
+  size_t rows, cols;
+  size_t t_vec_stride, t_col_stride;                   // in table rows
+  uint32_t* out;
+  size_t o_slice_stride, o_vec_stride, o_row_stride;   // in pair rows
+};
+
 struct FixedBaseArgs {
   ModCtxDev ctx;         // modulus n^2 (nr set)
   const uint32_t* table; // [nwin][2^w][L]

@@ -379,6 +379,18 @@ inline bool launch_wsum(int G, int K, const WsumArgs& a, unsigned blocks, unsign
          launch_wsum_part58(G, K, a, blocks, blocks_y, s) || launch_wsum_part59(G, K, a, blocks, blocks_y, s);
 }
 
+// The encrypted matrix product (hensel_matmul.hpp; k_hensel.hip parts 60-62): the matvec's multi-exponentiation for every
+// output of a tile of vectors over the window tables of launch_matvec_table, in the geometries matvec_has lists (the fold
+// of the column slices runs through the element-wise pair products, which have the (8,9) form)
+inline bool matmul_has(int G, int K) { return matvec_has(G, K); }
+bool launch_matmul_part60(int G, int K, const MatmulArgs& a, unsigned blocks, hipStream_t s);
+bool launch_matmul_part61(int G, int K, const MatmulArgs& a, unsigned blocks, hipStream_t s);
+bool launch_matmul_part62(int G, int K, const MatmulArgs& a, unsigned blocks, hipStream_t s);
+inline bool launch_matmul(int G, int K, const MatmulArgs& a, unsigned blocks, hipStream_t s) {
+  return launch_matmul_part60(G, K, a, blocks, s) || launch_matmul_part61(G, K, a, blocks, s) ||
+         launch_matmul_part62(G, K, a, blocks, s);
+}
+
 // DJN encrypt to pair rows in the same form (k_hensel.hip parts 20, 21, 28): (4,18) 2048-bit keys, (8,14) 3072, (2,19) 1024
 inline bool hensel_fb_encrypt_seq_has(int G, int K) { return (G == 4 && K == 18) || (G == 8 && K == 14) || (G == 2 && K == 19); }
 bool launch_hensel_fb_encrypt_seq_part28(int G, int K, const HenselFbArgs& a, unsigned blocks, hipStream_t s);

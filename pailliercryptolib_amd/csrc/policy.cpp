@@ -284,6 +284,71 @@ int matvec_window(size_t rows, size_t cols, int e_bits, size_t slices, size_t ro
 }
 
 
+// ---- encrypted matrix product ----
+// the matvec's slice rule without its knob (matvec_slices above: the same four lines)
+static size_t slices_rule(int G, size_t rows, size_t cols) {
+  const size_t ipw = 64 / (size_t)G;
+  const size_t row_waves = (rows + ipw - 1) / ipw;
+  const size_t fill = (kSimds + row_waves - 1) / row_waves;
+  const size_t cap = std::max<size_t>(1, cols / kMatvecMinSliceCols);
+  return std::max<size_t>(1, std::min(std::min(fill, cap), cols));
+}
+static size_t matmul_slices_with(long forced, int G, size_t t, size_t rows, size_t cols) {
+  if (forced > 0) return std::min((size_t)forced, cols);
+  return slices_rule(G, t * rows, cols);
+}
+static double matmul_products_with(long forced_s, int G, size_t n_vec, size_t rows, size_t cols, int e_bits, int w, size_t tile) {
+  const double nwin = (double)((e_bits + w - 1) / w);
+  const auto pass = [&](size_t t) {
+    const double S = (double)matmul_slices_with(forced_s, G, t, rows, cols), out = (double)t * (double)rows;
+    return (double)t * (double)cols * (double)(((size_t)1 << w) - 2) + out * S * (double)e_bits + out * (double)cols * nwin + out * (S - 1);
+  };
+  const size_t full = n_vec / tile, rem = n_vec % tile;
+  return (double)full * pass(tile) + (rem ? pass(rem) : 0.0);
+}
+size_t matmul_slices(int G, size_t t, size_t rows, size_t cols) {
+  if (t == 0 || rows == 0 || cols == 0) return 1;
+  return matmul_slices_with(env_now("PGPU_MATMUL_SLICES"), G, t, rows, cols);
+}
+double matmul_products(int G, size_t n_vec, size_t rows, size_t cols, int e_bits, int w, size_t tile) {
+  return matmul_products_with(env_now("PGPU_MATMUL_SLICES"), G, n_vec, rows, cols, e_bits, w, tile);
+}
+void matmul_plan(int G, size_t n_vec, size_t rows, size_t cols, int e_bits, size_t row_bytes, MatmulPlan* plan) {
+  const long fw = env_now("PGPU_MATMUL_WINDOW"), ft = env_now("PGPU_MATMUL_TILE"), fs = env_now("PGPU_MATMUL_SLICES");
+  const int w_lo = fw > 0 ? (int)std::min(fw, 6L) : 1, w_hi = fw > 0 ? w_lo : 6;
+  int best_w = w_lo;
+  size_t best_t = ft > 0 ? std::min((size_t)ft, n_vec) : 1;
+  double best_cost = -1;
+  for (int w = w_lo; w <= w_hi; ++w) {
+    // vectors whose tables fit the cap at this window; a forced value is taken as it is
+    size_t t_hi = 0;
+    if (cols <= kMatvecTableCap) t_hi = std::min(n_vec, kMatvecTableCap / (cols * ((size_t)1 << w) * row_bytes));
+    if (t_hi == 0) {
+      if (w > w_lo) break;
+      t_hi = 1;     // one oversized vector: tile = 1 at the smallest window
+    }
+    size_t t_lo = 1;
+    if (ft > 0) t_lo = t_hi = std::min((size_t)ft, n_vec);
+    for (size_t t = t_hi; t >= t_lo; --t) {
+      const double cost = matmul_products_with(fs, G, n_vec, rows, cols, e_bits, w, t);
+      // ties: the larger tile, then the smaller window
+      if (best_cost < 0 || cost < best_cost || (cost == best_cost && (t > best_t || (t == best_t && w < best_w)))) {
+        best_cost = cost;
+        best_w = w;
+        best_t = t;
+      }
+    }
+  }
+  plan->window = best_w;
+  plan->tile = best_t;
+  plan->passes = (n_vec + best_t - 1) / best_t;
+  plan->last = n_vec - (plan->passes - 1) * best_t;
+  plan->slices = matmul_slices_with(fs, G, best_t, rows, cols);
+  plan->last_slices = matmul_slices_with(fs, G, plan->last, rows, cols);
+  plan->products = best_cost;
+}
+
+
 // ---- encrypted segmented sum ----
 bool segsum_sort(const uint32_t* ids, size_t groups, size_t cols, size_t n_segments, std::vector<uint32_t>* perm,
                  std::vector<size_t>* offsets) {

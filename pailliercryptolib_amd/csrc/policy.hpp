@@ -135,6 +135,41 @@ int matvec_window(size_t rows, size_t cols, int e_bits, size_t slices, size_t ro
 double matvec_products(size_t rows, size_t cols, int e_bits, int w, size_t slices);
 
 
+// ---- the encrypted matrix product (hensel_matmul.hpp; pgpu_batch_ct_matmul, pgpu_ct_matmul_plan) ----
+// Y[v][i] = prod_j X[v][j]^W[i][j] for n_vec vectors: the matvec above, walked in TILES of `tile` vectors -- one pass
+// builds the window tables of its tile*cols ciphertexts, runs one group of G lanes per output (v, i) and column slice, and
+// folds the slices; the next pass reuses the table block.  A pass over t vectors costs, in pair products,
+//     t * cols * (2^w - 2)                table build
+//   + t * rows * S * e_bits               squarings
+//   + t * rows * cols * ceil(e_bits / w)  multiplications by table entries
+//   + t * rows * (S - 1)                  fold of the partial products,
+// with S the matvec's slice rule for the t * rows outputs of the pass (matvec_slices without its knob; the short last
+// pass of a call has its own S).  The table and the multiplications sum to the same whatever the tile; the tile decides
+// how many outputs a launch has, hence S, and -- the reason it exists -- how large a table one pass holds: under
+// kMatvecTableCap at the window the product count wants, however many vectors the call has.
+// matmul_plan: w in 1..6 and tile in 1..n_vec with tile * cols * 2^w * row_bytes <= kMatvecTableCap, the pair with the
+// fewest products of the whole call (ceil(n_vec / tile) passes, the last one short where tile does not divide n_vec);
+// ties go to the larger tile, then to the smaller window.  Where one vector's table at w = 1 exceeds the cap: tile = 1,
+// w = 1, as matvec_window leaves such a vector.  n_vec = 1 gives matvec_window and matvec_slices.
+// PGPU_MATMUL_WINDOW=w, PGPU_MATMUL_TILE=t, PGPU_MATMUL_SLICES=S force the three values (clamped to 1..6, 1..n_vec,
+// 1..cols; a forced S holds for every pass; a forced value is not held against the cap; read at every call: the tests
+// reach every path with them).
+struct MatmulPlan {
+  int window = 1;
+  size_t tile = 1;          // vectors of a full pass
+  size_t passes = 1;        // ceil(n_vec / tile)
+  size_t last = 1;          // vectors of the last pass: n_vec - (passes - 1) * tile, 1 .. tile
+  size_t slices = 1;        // S of a full pass
+  size_t last_slices = 1;   // S of the last pass (== slices where passes == 1 or last == tile)
+  double products = 0;
+};
+// S of a pass over t vectors under the rule above (forced: PGPU_MATMUL_SLICES)
+size_t matmul_slices(int G, size_t t, size_t rows, size_t cols);
+// products of the whole call for given w and tile, S by matmul_slices pass by pass
+double matmul_products(int G, size_t n_vec, size_t rows, size_t cols, int e_bits, int w, size_t tile);
+void matmul_plan(int G, size_t n_vec, size_t rows, size_t cols, int e_bits, size_t row_bytes, MatmulPlan* plan);
+
+
 // ---- the encrypted segmented sum (hensel_segsum.hpp; pgpu_batch_ct_segment_sum, pgpu_ct_segment_sum_plan) ----
 // out[g][s] = prod_{j : ids[g][j] == s} X[j].  A segment of m elements costs m - 1 pair products however it is cut, so the
 // cut decides only how the products spread over the chip and what each chain pays beside them.

@@ -190,6 +190,32 @@ class PublicKey:
         return self._resident_call([self._ct(x), (flat, ew)], len(rows), lambda L, h, out:
                                    L.pgpu_batch_ct_matvec(self._h, h[0], h[1], len(rows), int(e_bits), out))
 
+    def matmul(self, x, w, transposed=False, e_bits=None):
+        """Encrypted matrix product: x a list of n_vec lists of cols ciphertexts (ints modulo n^2), w a plaintext matrix
+        (a list of rows of cols non-negative ints) -> a list of n_vec lists of rows ciphertexts, out[v][i] =
+        prod_j x[v][j]^w[i][j] mod n^2, i.e. encryptions of (m @ w.T) mod n -- a linear layer applied to a minibatch.
+        transposed: x a list of cols lists of n_vec ciphertexts, the result a list of rows lists of n_vec, out[i][v] =
+        prod_j x[j][v]^w[i][j] mod n^2, i.e. encryptions of (w @ m) mod n.  One pgpu_batch_ct_matmul call on resident
+        batches (the matvec's multi-exponentiation per output, the vectors walked in tiles); there is no element-wise
+        fall-back."""
+        xs, rows = [list(r) for r in x], [list(r) for r in w]
+        if not xs or not xs[0] or not rows or any(len(r) != len(xs[0]) for r in xs):
+            raise RuntimeError("matmul error: Size mismatch!")
+        n_vec, cols = (len(xs[0]), len(xs)) if transposed else (len(xs), len(xs[0]))
+        if any(len(r) != cols for r in rows):
+            raise RuntimeError("matmul error: Size mismatch!")
+        flat = [int(v) for r in rows for v in r]
+        if min(flat) < 0:
+            raise RuntimeError("matmul error: negative weights have no encoding (pass w mod n)")
+        if e_bits is None:
+            e_bits = max(1, max(v.bit_length() for v in flat))
+        ew = (int(e_bits) + 63) // 64
+        out = self._resident_call([self._ct([c for r in xs for c in r]), (flat, ew)], n_vec * len(rows), lambda L, h, out:
+                                  L.pgpu_batch_ct_matmul(self._h, h[0], h[1], n_vec, len(rows), int(e_bits),
+                                                         1 if transposed else 0, out))
+        inner = n_vec if transposed else len(rows)
+        return [out[k:k + inner] for k in range(0, len(out), inner)]
+
     def spmv(self, x, indptr, indices, w, e_bits=None):
         """Encrypted sparse matrix-vector product: x a list of ciphertexts (ints modulo n^2), the plaintext matrix in CSR
         form -- indptr (rows + 1 offsets, starting at 0), indices (a column of x per entry), w (a non-negative int per
