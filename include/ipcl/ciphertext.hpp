@@ -14,6 +14,7 @@ namespace ipcl {
 class CipherText;
 namespace ext {   // include/ipcl/ext/linear.hpp
 CipherText matVec(const PlainText& w, std::size_t rows, const CipherText& x);
+CipherText matVecBucket(const PlainText& w, std::size_t rows, const CipherText& x);
 CipherText matMul(const PlainText& w, std::size_t rows, const CipherText& x, std::size_t n_vec, bool transposed);
 CipherText sparseMatVec(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx, const PlainText& w,
                         const CipherText& x);
@@ -51,6 +52,8 @@ class CipherText : public BaseText {
   friend class PublicKey;
   friend CipherText ext::matVec(const PlainText& w, std::size_t rows, const CipherText& x);
   CipherText linearMap(const PlainText& w, std::size_t rows) const;   // prod_j this[j]^w[i][j]: csrc/host/linear.cpp
+  friend CipherText ext::matVecBucket(const PlainText& w, std::size_t rows, const CipherText& x);
+  CipherText linearMapBucket(const PlainText& w, std::size_t rows) const;   // the same by the bucket method: csrc/host/linear.cpp
   friend CipherText ext::matMul(const PlainText& w, std::size_t rows, const CipherText& x, std::size_t n_vec, bool transposed);
   // prod_j this(v, j)^w[i][j] for the n_vec vectors this holds: csrc/host/linear.cpp
   CipherText linearMapBatch(const PlainText& w, std::size_t rows, std::size_t n_vec, bool transposed) const;

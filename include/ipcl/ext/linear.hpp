@@ -4,6 +4,12 @@
 //   matVec(w, rows, x)   y[i] = sum_j w[i*cols + j] * x[j]   under the encryption, cols = x.getSize():
 //                        Y[i] = prod_j X[j]^w[i][j] mod n^2 -- an encrypted linear layer, a weighted aggregate
 //   dot(w, x)            the rows = 1 case
+//   matVecBucket(w, rows, x)
+//                        matVec by the bucket method, the same arguments, errors and result bit for bit: for few rows over
+//                        very many columns, or weights of any width (a signed weight passed as w mod n).  One
+//                        pgpu_batch_ct_matvec_bucket call: no window tables -- per window of c bits the columns that
+//                        share a digit are multiplied into a bucket, the buckets reduced by running products, the
+//                        windows combined by Horner; the weights are read on the host.  matVec and dot never route here.
 //   matMul(w, rows, x, n_vec, transposed = false)
 //                        the same map for n_vec vectors at once, cols = x.getSize() / n_vec: x read as [n_vec][cols] and
 //                        the result as [n_vec][rows], Y[v][i] = prod_j X[v][j]^w[i][j] mod n^2 (Y = X * W^T: a linear layer
@@ -46,6 +52,7 @@ namespace ext {
 
 CipherText matVec(const PlainText& w, std::size_t rows, const CipherText& x);
 CipherText dot(const PlainText& w, const CipherText& x);
+CipherText matVecBucket(const PlainText& w, std::size_t rows, const CipherText& x);
 CipherText matMul(const PlainText& w, std::size_t rows, const CipherText& x, std::size_t n_vec, bool transposed = false);
 CipherText sparseMatVec(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx, const PlainText& w,
                         const CipherText& x);

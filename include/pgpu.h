@@ -501,6 +501,38 @@ int pgpu_batch_ct_matmul(const pgpu_pubkey* key, const pgpu_batch* x, const pgpu
  * pair rows for keys of key_bits. */
 int pgpu_ct_matmul_plan(int key_bits, size_t n_vec, size_t rows, size_t cols, int e_bits,
                         int* window, int* slices, size_t* tile, size_t* table_bytes, size_t* products);
+/* Bucket-method encrypted matrix-vector product: few rows over very many columns, or weights of any width (a signed
+ * weight sent as w mod n is full width).  x a resident ciphertext batch of cols elements (pair rows, or uploaded plain
+ * ciphertext words: converted on the way in); w HOST memory, rows*cols weights of w_words little-endian 64-bit words each,
+ * row-major, consumed before the call returns (the host cuts the digits, as pgpu_batch_ct_weighted_sum does):
+ *     out[i] = prod_j x[j]^(w[i*cols + j] mod 2^e_bits) mod n^2,      1 <= e_bits <= 64 * w_words,
+ * i.e. Dec(out) = W * Dec(x) mod n, bit for bit what pgpu_batch_ct_matvec returns.  A zero weight contributes 1 and an
+ * all-zero row yields the ciphertext 1.  There are no window tables: every weight is cut into ceil(e_bits / c) digits of
+ * c bits, the columns that share digit d of a (row, window) are multiplied into bucket d (a segmented sum: one product
+ * per column and window whatever c is), the buckets are reduced to prod_d B_d^d by running products in two levels, and
+ * the windows are combined by Horner ("Bucket-method matvec").  About rows * W * (cols + 2 * 2^c) products
+ * instead of rows * cols * e_bits.  The result is an ordinary resident ciphertext batch of `rows` elements in pair rows
+ * on the lane of x; x is left unchanged.  There is no fall-back to pgpu_batch_ct_matvec or to the element-wise route.
+ * PGPU_ERR_INVALID_PARAM: null / stale handles, rows == 0, w_words < 1, e_bits outside 1 .. 64 * w_words, ciphertext width
+ * mismatch, a batch of another key, rows * W * cols or rows * W * 2^c at or beyond 2^31 (what the descriptors address), a
+ * bucket block of more than 4 GiB (a forced window, or c = 1 where no window fits the plan's 256 MiB cap), a plan beyond host memory.
+ * PGPU_ERR_UNSUPPORTED: keys without pair rows (beyond 3072 bits; PGPU_PAIR_ROWS=0 / PGPU_HENSEL=0), pools of more than one
+ * GPU, and -- SIDE CHANNELS -- the masked table-gather policy: the ciphertext rows are addressed by digits of the PLAINTEXT
+ * weights (never by key material or by anything encrypted).
+ * All refusals are decided on the host before any launch and leave *out untouched. */
+int pgpu_batch_ct_matvec_bucket(const pgpu_pubkey* key, const pgpu_batch* x, const uint64_t* w, int w_words, size_t rows,
+                                int e_bits, pgpu_batch** out);
+/* What a call of this shape would run (host-side query, needs no device): the window c (1..10), the block b of the
+ * first reduction level (a power of two, 1..2^c), the bytes of the bucket block (rows * W * 2^c pair rows, W =
+ * ceil(e_bits / c)), and data-independent upper bounds of the pair products of the whole call -- rows*W*cols for the
+ * buckets, rows*W*nb*2(b-1) and rows*W*(2(nb-1) + log2 b + nb) for the two reduction levels (nb = 2^c / b),
+ * rows*(W-1)*(c+1) for Horner -- and of its depth, the products one after the other: the longest chain of every
+ * accumulation level, the two reduction chains, the Horner chain.  The rule is policy.hpp: bucket_plan;
+ * PGPU_BUCKET_WINDOW / PGPU_BUCKET_BLOCK force the two values, read at every call.
+ * PGPU_ERR_INVALID_PARAM: a size or e_bits that is not positive, a product count beyond size_t.  PGPU_ERR_UNSUPPORTED: no
+ * pair rows for keys of key_bits. */
+int pgpu_ct_matvec_bucket_plan(int key_bits, size_t rows, size_t cols, int e_bits, int* window, int* block,
+                               size_t* bucket_bytes, size_t* products, size_t* depth);
 
 /* ---- instrumentation used by bench.py (roofline) ----
  * With timing enabled every kernel launch is bracketed by two HIP events recorded on the stream
@@ -518,7 +550,8 @@ typedef enum pgpu_kernel_kind {
   PGPU_KERNEL_PACK = 8,       /* the launch of pgpu_batch_ct_pack */
   PGPU_KERNEL_SPMV = 9,       /* every launch of pgpu_batch_ct_spmv: table build, multi-exponentiation, fold levels */
   PGPU_KERNEL_WSUM = 10,      /* every launch of pgpu_batch_ct_weighted_sum: the slices' schedules, the fold */
-  PGPU_KERNEL_MATMUL = 11     /* every launch of pgpu_batch_ct_matmul: per pass the table build, the multi-exponentiation, the fold */
+  PGPU_KERNEL_MATMUL = 11,    /* every launch of pgpu_batch_ct_matmul: per pass the table build, the multi-exponentiation, the fold */
+  PGPU_KERNEL_BUCKET = 12     /* every launch of pgpu_batch_ct_matvec_bucket: accumulation levels, bucket reductions, Horner */
 } pgpu_kernel_kind;
 int pgpu_set_timing(int enabled);
 int pgpu_timing_collect(int* kinds, double* ms, int max_entries);

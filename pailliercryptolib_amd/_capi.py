@@ -42,6 +42,7 @@ SYMBOLS = [
     "pgpu_batch_ct_pack", "pgpu_ct_pack_plan",
     "pgpu_batch_ct_spmv", "pgpu_ct_spmv_plan",
     "pgpu_batch_ct_weighted_sum", "pgpu_ct_weighted_sum_plan",
+    "pgpu_batch_ct_matvec_bucket", "pgpu_ct_matvec_bucket_plan",
 ]
 FEATURE_4096_SPLIT = 1
 SEGMENT_NONE = 0xFFFFFFFF      # PGPU_SEGMENT_NONE: the element is left out of that group
@@ -177,6 +178,11 @@ def lib():
     L.pgpu_batch_ct_matvec.restype = c_int
     L.pgpu_ct_matvec_plan.argtypes = [c_int, c_size_t, c_size_t, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_size_t)]
     L.pgpu_ct_matvec_plan.restype = c_int
+    L.pgpu_batch_ct_matvec_bucket.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_int, POINTER(c_void_p)]
+    L.pgpu_batch_ct_matvec_bucket.restype = c_int
+    L.pgpu_ct_matvec_bucket_plan.argtypes = [c_int, c_size_t, c_size_t, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_size_t),
+                                             POINTER(c_size_t), POINTER(c_size_t)]
+    L.pgpu_ct_matvec_bucket_plan.restype = c_int
     L.pgpu_batch_ct_matmul.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_int, ctypes.c_uint, POINTER(c_void_p)]
     L.pgpu_batch_ct_matmul.restype = c_int
     L.pgpu_ct_matmul_plan.argtypes = [c_int, c_size_t, c_size_t, c_size_t, c_int, POINTER(c_int), POINTER(c_int),

@@ -1,4 +1,4 @@
-// pailliercryptolib_amd -- the aggregation calls on resident ciphertexts (pgpu_batch_ct_matvec / _matmul / _spmv / _weighted_sum /
+// pailliercryptolib_amd -- the aggregation calls on resident ciphertexts (pgpu_batch_ct_matvec / _matvec_bucket / _matmul / _spmv / _weighted_sum /
 // _segment_sum / _segment_scan / _pack) and their plan queries (pgpu_ct_*_plan).
 // Part of the translation unit of capi.cpp (included there, in place, after capi_batches.inc, whose bounce buffer the plan
 // upload shares).  Every call is: its own parameter checks, the admission tail, its plan (policy.hpp), the result set-up,
@@ -328,6 +328,130 @@ int pgpu_batch_ct_matmul(const pgpu_pubkey* key, const pgpu_batch* x, const pgpu
       HIP_TRY(hipMemcpy2DAsync(dest, n_vec * row_bytes, partial.p, t * row_bytes, t * row_bytes, rows, hipMemcpyDeviceToDevice, r.s));
   }
   RC_TRY(lanes_order(w, r.x->lane, false));
+  return r.finish(out);
+}
+
+// ---- bucket-method encrypted matvec (hensel_bucket.hpp; policy.hpp: bucket_*) ----
+int pgpu_ct_matvec_bucket_plan(int key_bits, size_t rows, size_t cols, int e_bits, int* window, int* block,
+                               size_t* bucket_bytes, size_t* products, size_t* depth) {
+  if (key_bits < 1 || rows == 0 || cols == 0 || e_bits < 1)
+    return fail(PGPU_ERR_INVALID_PARAM, "bucket matvec plan: key_bits, rows, cols and e_bits must be positive");
+  int G = 0, K = 0;
+  if (!policy::matvec_geometry(key_bits, &G, &K))
+    return fail(PGPU_ERR_UNSUPPORTED, "bucket matvec: keys of this size have no pair rows (1024- to 3072-bit key classes only)");
+  policy::BucketPlan plan;
+  policy::bucket_plan(G, rows, cols, e_bits, (size_t)2 * G * K * sizeof(uint32_t), &plan);
+  if (plan.products >= 18446744073709551615.0) return fail(PGPU_ERR_INVALID_PARAM, "bucket matvec plan: the product count overflows");
+  if (window) *window = plan.window;
+  if (block) *block = plan.block;
+  if (bucket_bytes) *bucket_bytes = plan.bucket_bytes;
+  if (products) *products = (size_t)plan.products;
+  if (depth) *depth = plan.depth;
+  return PGPU_OK;
+}
+
+int pgpu_batch_ct_matvec_bucket(const pgpu_pubkey* key, const pgpu_batch* x, const uint64_t* w, int w_words, size_t rows,
+                                int e_bits, pgpu_batch** out) {
+  RC_TRY(rt::check_ready());
+  if (!key || !x || !w || !out) return fail(PGPU_ERR_INVALID_PARAM, "null argument");
+  RC_TRY(check_gen(key->gen, "key"));
+  RC_TRY(check_gen(x->gen, "batch"));
+  const size_t cols = x->count;
+  if (rows == 0) return fail(PGPU_ERR_INVALID_PARAM, "bucket matvec error: rows must be positive");
+  if (w_words < 1) return fail(PGPU_ERR_INVALID_PARAM, "bucket matvec error: w_words must be positive");
+  if (e_bits < 1 || e_bits > 64 * (long)w_words) return fail(PGPU_ERR_INVALID_PARAM, "bucket matvec error: e_bits outside 1 .. 64 * w_words");
+  if (cols == 0) return fail(PGPU_ERR_INVALID_PARAM, "bucket matvec error: empty batch");
+  if (x->words != 2 * key->n_words) return fail(PGPU_ERR_INVALID_PARAM, "bucket matvec error: ciphertext width mismatch");
+  static const AggOp op{"bucket matvec", "rows", " and this call addresses the ciphertext rows by digits of the plaintext weights; no masked variant exists",
+                        pgpu::bucket_has, nullptr};
+  const pgpu_pubkey::PubForm* pf = nullptr;
+  RC_TRY(agg_admit(op, key, &x, 1, &pf));
+  // the plan, on the host: window and block, then the accumulation as a segmented sum over rows * W groups of 2^c buckets
+  const int G = pf->H;
+  const size_t LQ = (size_t)2 * pf->H * pf->K, row_bytes = LQ * sizeof(uint32_t);
+  policy::BucketPlan bp;
+  policy::bucket_plan(G, rows, cols, e_bits, row_bytes, &bp);
+  const int c = bp.window;
+  const size_t W = bp.windows, b = (size_t)bp.block, nb = bp.nb, nseg = (size_t)1 << c;
+  // (element numbers are 32-bit entries of the sorted list, bucket and partial-row numbers 31-bit fields of a descriptor)
+  constexpr size_t kMax = (size_t)1 << 31;
+  if (cols >= kMax || rows >= kMax / W || rows * W >= kMax / cols || rows * W >= kMax / nseg)
+    return fail(PGPU_ERR_INVALID_PARAM, "bucket matvec error: rows * windows * count(x) and rows * windows * 2^window must stay below 2^31");
+  const size_t groups = rows * W;
+  // (a forced window, or the c = 1 that stands in where no window fits the cap, is not held against kMatvecTableCap: this
+  // bounds the bucket block on the device and the two counters per bucket of the host's sort before either is allocated)
+  if (groups * nseg > policy::kBucketBlockMax / row_bytes)
+    return fail(PGPU_ERR_INVALID_PARAM, "bucket matvec error: the bucket block (rows * windows * 2^window pair rows) exceeds 4 GiB");
+  std::vector<uint32_t> perm;
+  std::vector<size_t> offsets;
+  policy::SegsumPlan plan;
+  policy::SegsumImage img;
+  try {
+    policy::bucket_sort(w, w_words, rows, cols, e_bits, c, &perm, &offsets);
+    policy::segsum_plan(offsets, policy::segsum_chunk(G, groups * cols), &plan);
+    policy::segsum_image(perm, plan, &img);
+  } catch (const std::bad_alloc&) {
+    return fail(PGPU_ERR_INVALID_PARAM, "bucket matvec error: the sorted column list and its plan do not fit host memory (fewer rows or columns per call)");
+  }
+  AggRun r;
+  RC_TRY(r.open(key, pf, x, rows));
+  // buckets [rows][W][2^c], the blocks' U and V [rows][W][nb] each, the windows' S [rows][W]: the block arena, on the lane's stream
+  const bool two_levels = b > 1 && nb > 1;
+  rt::DevMem dimage, partial, buckets, uv, sw;
+  RC_TRY(buckets.alloc(*r.dev, r.s, groups * nseg * row_bytes));
+  if (two_levels) RC_TRY(uv.alloc(*r.dev, r.s, 2 * groups * nb * row_bytes));
+  if (W > 1) RC_TRY(sw.alloc(*r.dev, r.s, groups * row_bytes));
+  if (img.region[0]) RC_TRY(partial.alloc(*r.dev, r.s, (img.region[0] + img.region[1]) * row_bytes));
+  RC_TRY(upload_plan_image(*r.dev, r.s, img.image.data(), img.image.size(), &dimage));
+  const pgpu_pubkey::PubForm* wide = wide_form(key, pf, pgpu::segsum_wide_has);
+  uint32_t* const reg[2] = {(uint32_t*)partial.p, partial.p ? (uint32_t*)partial.p + img.region[0] * LQ : nullptr};
+  for (size_t l = 0; l < plan.levels.size(); ++l)
+    RC_TRY(segsum_level(r, wide, l == 0 ? r.x->prow(0) : reg[(l - 1) & 1], l == 0 ? (const uint32_t*)dimage.p : nullptr,
+                        (const char*)dimage.p + img.level_at[l], plan.levels[l].chunks.size(), (uint32_t*)buckets.p, reg[l & 1],
+                        PGPU_KERNEL_BUCKET));
+  // the reductions: every launch in the wide form where its chains leave SIMDs empty (policy.hpp: segsum_wide_pays)
+  const pgpu_pubkey::PubForm* bwide = wide_form(key, pf, pgpu::bucket_wide_has);
+  auto reduce = [&](pgpu::BucketArgs& a) -> int {
+    const pgpu_pubkey::PubForm* lf = bwide && policy::segsum_wide_pays(bwide->H, a.chains) ? bwide : pf;
+    a.ctx = hensel_pub_view(lf, r.dev->index);
+    return timed_launch(r, a.chains, lf->H, PGPU_KERNEL_BUCKET, "bucket matvec",
+                        [&](unsigned blocks) { return pgpu::launch_bucket(lf->H, lf->K, a, blocks, r.s); });
+  };
+  uint32_t* const s_out = W > 1 ? (uint32_t*)sw.p : r.o->prow(0);
+  uint32_t* const U = (uint32_t*)uv.p;
+  uint32_t* const V = two_levels ? U + groups * nb * LQ : nullptr;
+  if (b > 1) {          // level 1: one chain per block (nb == 1: tot is S itself)
+    pgpu::BucketArgs a{};
+    a.src = (const uint32_t*)buckets.p;
+    a.chains = groups * nb;
+    a.len = (uint32_t)b;
+    a.out_acc = two_levels ? U : nullptr;
+    a.out_tot = two_levels ? V : s_out;
+    RC_TRY(reduce(a));
+  }
+  if (nb > 1) {         // level 2: one chain per (row, window) (b == 1: over the buckets themselves, U = B and every V is one)
+    pgpu::BucketArgs a{};
+    a.src = two_levels ? U : (const uint32_t*)buckets.p;
+    a.mul = V;
+    a.chains = groups;
+    a.len = (uint32_t)nb;
+    a.n_sqr = two_levels ? (uint32_t)policy::bucket_log2(b) : 0;
+    a.n_mul = two_levels ? (uint32_t)nb : 0;
+    a.out_tot = s_out;
+    RC_TRY(reduce(a));
+  }
+  if (W > 1) {          // Horner across the windows: the slot packing's kernel over S as [rows][W], window 0 least significant
+    const pgpu_pubkey::PubForm* pwide = wide_form(key, pf, pgpu::pack_wide_has);
+    const pgpu_pubkey::PubForm* lf = pwide && policy::segsum_wide_pays(pwide->H, rows) ? pwide : pf;
+    pgpu::PackArgs a{};
+    a.ctx = hensel_pub_view(lf, r.dev->index);
+    a.src = (const uint32_t*)sw.p;
+    a.rows = rows;
+    a.seg_len = (uint32_t)W;
+    a.slot_bits = (uint32_t)c;
+    a.out = r.o->prow(0);
+    RC_TRY(timed_launch(r, rows, lf->H, PGPU_KERNEL_BUCKET, "bucket matvec", [&](unsigned blocks) { return pgpu::launch_pack(lf->H, lf->K, a, blocks, r.s); }));
+  }
   return r.finish(out);
 }
 

@@ -1,5 +1,5 @@
-// ipcl::ext::matVec / dot / matMul / sparseMatVec / weightedSum / sum -- linear maps on encrypted vectors (include/ipcl/ext/linear.hpp): one
-// pgpu_batch_ct_matvec / pgpu_batch_ct_matmul / pgpu_batch_ct_spmv / pgpu_batch_ct_weighted_sum call on resident batches.  The reference composes such a map from CipherText::operator*
+// ipcl::ext::matVec / dot / matVecBucket / matMul / sparseMatVec / weightedSum / sum -- linear maps on encrypted vectors (include/ipcl/ext/linear.hpp): one
+// pgpu_batch_ct_matvec / pgpu_batch_ct_matvec_bucket / pgpu_batch_ct_matmul / pgpu_batch_ct_spmv / pgpu_batch_ct_weighted_sum call on resident batches.  The reference composes such a map from CipherText::operator*
 // (ciphertext.cpp:83-106) and operator+ (ciphertext.cpp:35-72) term by term.
 #include "ipcl/ext/linear.hpp"
 
@@ -21,6 +21,32 @@ CipherText CipherText::linearMap(const PlainText& w, std::size_t rows) const {
   auto dx = deviceBatch(W, &nsq), dw = w.deviceBatch(ew);
   pgpu_batch* o = nullptr;
   IPCL_GPU_CHECK(pgpu_batch_ct_matvec(m_pk->device()->h, dx->h, dw->h, rows, ebits, &o), "matVec");
+  return CipherText(m_pk, detail::DeviceBatch::adopt(o));
+}
+
+CipherText CipherText::linearMapBucket(const PlainText& w, std::size_t rows) const {
+  ERROR_CHECK(m_size > 0, "matVec error: empty CipherText");
+  ERROR_CHECK(rows > 0 && w.getSize() / rows == m_size && w.getSize() % rows == 0, "matVec error: Size mismatch!");
+  const BigNumber& nsq = *(m_pk->getNSQ());
+  const int W = detail::words_for_bits(nsq.BitSize());
+  // the weights as host words: the digits are cut from them, the device never reads them
+  const std::vector<BigNumber> a = w.getTexts();
+  int ebits = 1;
+  for (const auto& e : a) {
+    ERROR_CHECK(!e.isNegative(), "matVec error: negative plaintext");
+    ebits = std::max(ebits, e.BitSize());
+  }
+  const int ww = detail::words_for_bits(ebits);
+  std::vector<uint64_t> words(a.size() * (size_t)ww, 0);
+  std::vector<Ipp32u> v;
+  for (size_t k = 0; k < a.size(); ++k) {
+    v.clear();
+    a[k].num2vec(v);
+    for (size_t j = 0; j < v.size() && j < (size_t)2 * ww; ++j) words[k * (size_t)ww + j / 2] |= (uint64_t)v[j] << (32 * (j & 1));
+  }
+  auto dx = deviceBatch(W, &nsq);
+  pgpu_batch* o = nullptr;
+  IPCL_GPU_CHECK(pgpu_batch_ct_matvec_bucket(m_pk->device()->h, dx->h, words.data(), ww, rows, ebits, &o), "matVecBucket");
   return CipherText(m_pk, detail::DeviceBatch::adopt(o));
 }
 
@@ -110,6 +136,7 @@ CipherText weightedSum(const std::vector<CipherText>& xs, const PlainText& w) { 
 CipherText sum(const std::vector<CipherText>& xs) { return CipherText::weightedSumMap(xs, nullptr); }
 CipherText matVec(const PlainText& w, std::size_t rows, const CipherText& x) { return x.linearMap(w, rows); }
 CipherText dot(const PlainText& w, const CipherText& x) { return matVec(w, 1, x); }
+CipherText matVecBucket(const PlainText& w, std::size_t rows, const CipherText& x) { return x.linearMapBucket(w, rows); }
 CipherText matMul(const PlainText& w, std::size_t rows, const CipherText& x, std::size_t n_vec, bool transposed) {
   return x.linearMapBatch(w, rows, n_vec, transposed);
 }

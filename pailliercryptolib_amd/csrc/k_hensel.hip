@@ -1,5 +1,5 @@
 // pailliercryptolib_amd -- instantiations of the split-form CRT-decrypt exponentiation (hensel.hpp), split over
-// PGPU_PART = 0..62 so that they compile in parallel (60-62: the encrypted matrix product; 56-59: the encrypted weighted sum of K resident batches; 53-55: the encrypted sparse matrix-vector product; 38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 45-47: the encrypted segmented prefix sum; 48-51: the encrypted slot packing; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
+// PGPU_PART = 0..66 so that they compile in parallel (63-66: the bucket reduction of the bucket-method matvec; 60-62: the encrypted matrix product; 56-59: the encrypted weighted sum of K resident batches; 53-55: the encrypted sparse matrix-vector product; 38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 45-47: the encrypted segmented prefix sum; 48-51: the encrypted slot packing; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
 // the two-wavefronts-per-SIMD build of the (2,19) decrypt form; 11-13: element-wise operations on pair rows).
 #include "hensel_seq.hpp"
 #include "launch.hpp"
@@ -36,9 +36,12 @@
 #if defined(PGPU_PART) && PGPU_PART >= 60 && PGPU_PART <= 62
 #include "hensel_matmul.hpp"    // the encrypted matrix product: the matvec's schedule over a tile of vectors
 #endif
+#if defined(PGPU_PART) && PGPU_PART >= 63 && PGPU_PART <= 66
+#include "hensel_bucket.hpp"    // the bucket-method matvec: two running products per chain of buckets
+#endif
 
 #ifndef PGPU_PART
-#error "compile with -DPGPU_PART=0..62 (15 and 30 are retired)"
+#error "compile with -DPGPU_PART=0..66 (15 and 30 are retired)"
 #endif
 
 namespace pgpu {
@@ -626,6 +629,30 @@ bool PGPU_WS_NAME(int G, int K, const WsumArgs& a, unsigned blocks, unsigned blo
 bool PGPU_MM_NAME(int G, int K, const MatmulArgs& a, unsigned blocks, hipStream_t s) {
   if (G != PGPU_MM_G || K != PGPU_MM_K) return false;
   hipLaunchKernelGGL((matmul_kernel<PGPU_MM_G, PGPU_MM_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
+  return true;
+}
+#elif PGPU_PART >= 63 && PGPU_PART <= 66
+// the bucket reduction of the bucket-method matvec (hensel_bucket.hpp): one geometry per part; 66 is the 2048-bit class on 8 lanes
+#if PGPU_PART == 63
+#define PGPU_BK_G 2
+#define PGPU_BK_K 19
+#define PGPU_BK_NAME launch_bucket_part63
+#elif PGPU_PART == 64
+#define PGPU_BK_G 4
+#define PGPU_BK_K 18
+#define PGPU_BK_NAME launch_bucket_part64
+#elif PGPU_PART == 65
+#define PGPU_BK_G 8
+#define PGPU_BK_K 14
+#define PGPU_BK_NAME launch_bucket_part65
+#else
+#define PGPU_BK_G 8
+#define PGPU_BK_K 9
+#define PGPU_BK_NAME launch_bucket_part66
+#endif
+bool PGPU_BK_NAME(int G, int K, const BucketArgs& a, unsigned blocks, hipStream_t s) {
+  if (G != PGPU_BK_G || K != PGPU_BK_K) return false;
+  hipLaunchKernelGGL((bucket_reduce_kernel<PGPU_BK_G, PGPU_BK_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
   return true;
 }
 #else

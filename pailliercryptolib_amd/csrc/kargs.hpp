@@ -441,6 +441,25 @@ struct MatmulArgs {
   size_t o_slice_stride, o_vec_stride, o_row_stride;   // in pair rows
 };
 
+// Bucket reduction of the bucket-method matvec on pair rows (hensel_bucket.hpp): one chain per row of `src` read as
+// [chains][len], two running products walked from entry len - 1 down to entry 1,
+//     acc = prod_{i >= 1} src[i],   tot = prod_{i >= 1} src[i]^i        (2 (len - 2) products; len >= 2)
+// then, launch-uniform:
+//   out_acc != null  acc is multiplied by entry 0 and stored: U = prod_i src[i]                          (level 1)
+//   n_sqr, n_mul     tot is squared n_sqr times and multiplied by the rows mul[chain][0 .. n_mul - 1]     (level 2)
+// and tot is stored to out_tot.  No descriptors: every chain of a launch has the same trip count, and the rows are
+// addressed by arithmetic on chains, len and n_mul alone.  The stored rows come out of seq_pairmul or are input rows.
+struct BucketArgs {
+  HenselPubDev ctx;
+  const uint32_t* src;       // [chains * len][2*L2] pair rows
+  const uint32_t* mul;       // [chains * n_mul][2*L2] pair rows (n_mul == 0: not read)
+  size_t chains;             // >= 1
+  uint32_t len;              // >= 2
+  uint32_t n_sqr, n_mul;
+  uint32_t* out_acc;         // [chains][2*L2], or null
+  uint32_t* out_tot;         // [chains][2*L2], never the same memory as src or mul
+};
+
 struct FixedBaseArgs {
   ModCtxDev ctx;         // modulus n^2 (nr set)
   const uint32_t* table; // [nwin][2^w][L]

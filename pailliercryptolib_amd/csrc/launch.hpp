@@ -391,6 +391,20 @@ inline bool launch_matmul(int G, int K, const MatmulArgs& a, unsigned blocks, hi
          launch_matmul_part62(G, K, a, blocks, s);
 }
 
+// The bucket reduction of the bucket-method matvec (hensel_bucket.hpp; k_hensel.hip parts 63-66): two running products
+// per chain of buckets, in the geometries matvec_has lists, and -- part 66 -- with the 72 limbs of a 2048-bit key's half
+// on 8 lanes instead of 4, as the segmented sum and the packing have it: launches that leave SIMDs empty
+inline bool bucket_has(int G, int K) { return matvec_has(G, K); }
+inline bool bucket_wide_has(int G, int K) { return G == 8 && K == 9; }
+bool launch_bucket_part63(int G, int K, const BucketArgs& a, unsigned blocks, hipStream_t s);
+bool launch_bucket_part64(int G, int K, const BucketArgs& a, unsigned blocks, hipStream_t s);
+bool launch_bucket_part65(int G, int K, const BucketArgs& a, unsigned blocks, hipStream_t s);
+bool launch_bucket_part66(int G, int K, const BucketArgs& a, unsigned blocks, hipStream_t s);
+inline bool launch_bucket(int G, int K, const BucketArgs& a, unsigned blocks, hipStream_t s) {
+  return launch_bucket_part63(G, K, a, blocks, s) || launch_bucket_part64(G, K, a, blocks, s) ||
+         launch_bucket_part65(G, K, a, blocks, s) || launch_bucket_part66(G, K, a, blocks, s);
+}
+
 // DJN encrypt to pair rows in the same form (k_hensel.hip parts 20, 21, 28): (4,18) 2048-bit keys, (8,14) 3072, (2,19) 1024
 inline bool hensel_fb_encrypt_seq_has(int G, int K) { return (G == 4 && K == 18) || (G == 8 && K == 14) || (G == 2 && K == 19); }
 bool launch_hensel_fb_encrypt_seq_part28(int G, int K, const HenselFbArgs& a, unsigned blocks, hipStream_t s);

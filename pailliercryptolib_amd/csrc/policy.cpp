@@ -430,6 +430,93 @@ void segsum_plan(const std::vector<size_t>& offsets, int chunk, SegsumPlan* plan
 }
 
 
+// ---- bucket-method encrypted matvec ----
+int bucket_default_block(int c) { return 1 << ((c + 1) / 2); }
+int bucket_log2(size_t v) {
+  int l = 0;
+  while (((size_t)1 << (l + 1)) <= v) ++l;
+  return l;
+}
+double bucket_products(size_t rows, size_t cols, int e_bits, int c, int b) {
+  const double W = (double)((e_bits + c - 1) / c), nb = (double)(((size_t)1 << c) / (size_t)b), r = (double)rows;
+  return r * W * (double)cols + r * W * nb * 2.0 * (double)(b - 1) +
+         r * W * (2.0 * (nb - 1) + (double)bucket_log2((size_t)b) + nb) + r * (W - 1) * (double)(c + 1);
+}
+size_t bucket_depth(int G, size_t rows, size_t cols, int e_bits, int c, int b) {
+  const size_t W = (size_t)((e_bits + c - 1) / c), nb = ((size_t)1 << c) / (size_t)b;
+  const size_t groups = rows > ~(size_t)0 / W ? ~(size_t)0 : rows * W;
+  const size_t chunk = (size_t)segsum_chunk(G, cols && groups > ~(size_t)0 / cols ? ~(size_t)0 : groups * cols);
+  size_t depth = 0;
+  for (size_t m = cols;; m = (m + chunk - 1) / chunk) {
+    depth += std::min(chunk, m);
+    if (m <= chunk) break;
+  }
+  return depth + 2 * ((size_t)b - 1) + 2 * (nb - 1) + (size_t)bucket_log2((size_t)b) + nb + (W - 1) * (size_t)(c + 1);
+}
+void bucket_plan(int G, size_t rows, size_t cols, int e_bits, size_t row_bytes, BucketPlan* plan, double depth_weight) {
+  const long fc = env_now("PGPU_BUCKET_WINDOW"), fb = env_now("PGPU_BUCKET_BLOCK");
+  const int c_lo = fc > 0 ? (int)std::min(fc, (long)kBucketMaxWindow) : 1, c_hi = fc > 0 ? c_lo : kBucketMaxWindow;
+  const double chains = (double)(kSimds * 2 * (64 / (size_t)G));
+  int best_c = c_lo, best_b = 1;
+  double best_cost = -1;
+  for (int c = c_lo; c <= c_hi; ++c) {
+    const double W = (double)((e_bits + c - 1) / c);
+    // (a forced window is taken as it is; c = 1 stands in where no window fits the cap)
+    if (fc <= 0 && c > 1 && (double)rows * W * (double)((size_t)1 << c) * (double)row_bytes > (double)kMatvecTableCap) continue;
+    int b = bucket_default_block(c);
+    if (fb > 0) b = 1 << bucket_log2((size_t)std::min(fb, 1L << c));
+    const double cost = bucket_products(rows, cols, e_bits, c, b) / chains + depth_weight * (double)bucket_depth(G, rows, cols, e_bits, c, b);
+    if (best_cost < 0 || cost < best_cost) {     // (rising c: ties stay with the smaller one)
+      best_cost = cost;
+      best_c = c;
+      best_b = b;
+    }
+  }
+  plan->window = best_c;
+  plan->block = best_b;
+  plan->windows = (size_t)((e_bits + best_c - 1) / best_c);
+  plan->nb = ((size_t)1 << best_c) / (size_t)best_b;
+  const double bytes = (double)rows * (double)plan->windows * (double)((size_t)1 << best_c) * (double)row_bytes;
+  plan->bucket_bytes = bytes >= 18446744073709551615.0 ? ~(size_t)0 : (size_t)bytes;
+  plan->products = bucket_products(rows, cols, e_bits, best_c, best_b);
+  plan->depth = bucket_depth(G, rows, cols, e_bits, best_c, best_b);
+}
+// digit t of a weight: the bits c t .. min(c t + c, e_bits) - 1 (the top window may be narrower than c)
+static inline uint32_t bucket_digit(const uint64_t* v, int e_bits, int c, size_t t) {
+  const size_t lo = t * (size_t)c;
+  const int width = (int)std::min((size_t)c, (size_t)e_bits - lo), sh = (int)(lo % 64);
+  uint64_t d = v[lo / 64] >> sh;
+  if (sh + width > 64) d |= v[lo / 64 + 1] << (64 - sh);   // (the word above exists: the digit ends below e_bits)
+  return (uint32_t)(d & (((uint64_t)1 << width) - 1));
+}
+void bucket_sort(const uint64_t* w, int w_words, size_t rows, size_t cols, int e_bits, int c, std::vector<uint32_t>* perm,
+                 std::vector<size_t>* offsets) {
+  const size_t W = (size_t)((e_bits + c - 1) / c), nseg = (size_t)1 << c, segments = rows * W * nseg;
+  std::vector<size_t> off(segments + 1, 0);
+  for (size_t i = 0; i < rows; ++i)
+    for (size_t j = 0; j < cols; ++j) {
+      const uint64_t* v = w + (i * cols + j) * (size_t)w_words;
+      for (size_t t = 0; t < W; ++t) {
+        const uint32_t d = bucket_digit(v, e_bits, c, t);
+        if (d) ++off[(i * W + t) * nseg + d + 1];
+      }
+    }
+  for (size_t s = 0; s < segments; ++s) off[s + 1] += off[s];
+  std::vector<uint32_t> p(off[segments]);
+  std::vector<size_t> next(off.begin(), off.end() - 1);
+  for (size_t i = 0; i < rows; ++i)
+    for (size_t j = 0; j < cols; ++j) {   // rising j within every (row, window): equal digits keep their order
+      const uint64_t* v = w + (i * cols + j) * (size_t)w_words;
+      for (size_t t = 0; t < W; ++t) {
+        const uint32_t d = bucket_digit(v, e_bits, c, t);
+        if (d) p[next[(i * W + t) * nseg + d]++] = (uint32_t)j;
+      }
+    }
+  perm->swap(p);
+  offsets->swap(off);
+}
+
+
 // ---- encrypted sparse matrix-vector product ----
 int spmv_chunk(int G, size_t nnz, size_t rows) {
   (void)rows;

@@ -375,6 +375,68 @@ struct WsumPlan {
 bool wsum_plan(const uint64_t* weights, int w_words, size_t n_terms, size_t S, WsumPlan* plan);
 
 
+// ---- the bucket-method encrypted matvec (hensel_bucket.hpp; pgpu_batch_ct_matvec_bucket, pgpu_ct_matvec_bucket_plan) ----
+// Y[i] = prod_j X[j]^W[i][j] without window tables: every weight is cut into W = ceil(e_bits / c) digits of c bits, and
+// per (row, window)
+//   accumulate   the columns whose digit is d >= 1 are multiplied into bucket B_d: a segmented sum over rows * W groups
+//                of 2^c segments (bucket 0 and every empty bucket: the row of one), the levels of segsum_plan
+//   reduce 1     per block k of b buckets (b a power of two, nb = 2^c / b):  U_k = prod_i B[k b + i],
+//                V_k = prod_i B[k b + i]^i, by two running products                        (b == 1: skipped, U = B)
+//   reduce 2     S = prod_k V_k * (prod_k U_k^k)^b = prod_d B_d^d: the same two running products over the U_k, log2 b
+//                squarings, nb products by the V_k                                          (nb == 1: skipped, S = V_0)
+//   Horner       out[i] = prod_t S[i][t]^(2^(c t)): pack_kernel over [rows][W] with slot_bits = c (W == 1: no launch)
+// Counted in pair products, data-independent upper bounds (a chain that starts from its first entry instead of a one
+// saves a product or two of them):
+//     rows * W * cols                          accumulate
+//   + rows * W * nb * 2 (b - 1)                reduce 1
+//   + rows * W * (2 (nb - 1) + log2 b + nb)    reduce 2
+//   + rows * (W - 1) * (c + 1)                 Horner
+// and in depth -- the products of the call that run one after the other: the longest chain of every accumulation level
+// for a bucket that holds every column (chunk = segsum_chunk(G, rows * W * cols): min(chunk, m) at a level of m entries,
+// m -> ceil(m / chunk)), 2 (b - 1), 2 (nb - 1) + log2 b + nb, (W - 1) (c + 1).
+// bucket_plan: c in 1..kBucketMaxWindow, b = 2^ceil(c / 2); among the c whose bucket block rows * W * 2^c * row_bytes
+// stays under kMatvecTableCap (none: c = 1) the one that minimises  products / C + kBucketDepthWeight * depth,  with
+// C = kSimds * 2 wavefronts * 64 / G chains at work at a time; ties go to the smaller c.  The depth term is there
+// because the product count alone does not see serial reductions: at 2^20 columns of 32 bits c = 8, 9 and 10 are within
+// 0.15 % of each other in products (the same W), and c = 10 runs 87 serial products more than c = 8: 8.1 against 6.9 ms.
+// PGPU_BUCKET_WINDOW=c and PGPU_BUCKET_BLOCK=b force the two values (clamped to 1..kBucketMaxWindow and 1..2^c, a forced b
+// rounded down to a power of two; a forced value is not held against the cap; read at every call: the tests reach every
+// path with them).
+constexpr int kBucketMaxWindow = 10;
+// what the call refuses whatever chose the window: a bucket block beyond this many bytes (7.4 M buckets of a 2048-bit key)
+constexpr size_t kBucketBlockMax = (size_t)4 << 30;
+// kBucketDepthWeight, from the sweep of tools/bench_bucket.py --sweep (one MI355X, 2048-bit key, forced c = 4..10 at the
+// default block; profiles/bucket_bench.txt).  Kernel ms at 1 x 2^20 x 32 / 16 x 65536 x 32:
+//     c        4      5      6      7      8      9      10
+//     ms   11.51  10.89   9.58   8.51   6.98   7.73   8.20   /   11.16  10.04   8.95   8.07   6.67   7.44   7.87
+// A least-squares fit  ms = alpha * products + beta * depth + gamma  gives alpha = 1.04 / 1.07 ns, beta = 9.2 / 11.8 us:
+// beta / (alpha * C) = 0.27 / 0.34.  With 0.3 the cost orders all seven windows as measured at both shapes
+// (8 < 9 < 10 < 7 < 6 < 5 < 4); the first guess, 1, picked the same winner but put 7 ahead of 9 and 10.  Fitted on these
+// two shapes only.
+constexpr double kBucketDepthWeight = 0.3;
+struct BucketPlan {
+  int window = 1;           // c
+  int block = 1;            // b
+  size_t windows = 1;       // W = ceil(e_bits / c)
+  size_t nb = 2;            // 2^c / b
+  size_t bucket_bytes = 0;  // rows * W * 2^c * row_bytes
+  double products = 0;
+  size_t depth = 0;
+};
+int bucket_default_block(int c);
+int bucket_log2(size_t v);      // floor(log2 v), v >= 1
+double bucket_products(size_t rows, size_t cols, int e_bits, int c, int b);
+size_t bucket_depth(int G, size_t rows, size_t cols, int e_bits, int c, int b);
+// (depth_weight: the rule with another weight -- the tests construct exact ties at 0; at 0.3, no binary fraction, a tie is a matter of rounding)
+void bucket_plan(int G, size_t rows, size_t cols, int e_bits, size_t row_bytes, BucketPlan* plan,
+                 double depth_weight = kBucketDepthWeight);
+// the accumulation's sort, digit-aware: what segsum_sort makes of ids[(i * W + t) * cols + j] = digit t of w[i * cols + j]
+// (zero: kSegsumNone) over rows * W groups of 2^c segments, without materialising the ids -- a stable counting sort.
+// w: [rows * cols][w_words] little-endian 64-bit words; bits at and above e_bits are ignored.
+void bucket_sort(const uint64_t* w, int w_words, size_t rows, size_t cols, int e_bits, int c, std::vector<uint32_t>* perm,
+                 std::vector<size_t>* offsets);
+
+
 // ---- plan images: what an aggregation call uploads in one copy (capi_aggregate.inc) ----
 // Sections one after the other; add() pads with zero bytes up to a multiple of `align` first and returns the byte offset
 // of the section.  src == null leaves the n bytes zero.

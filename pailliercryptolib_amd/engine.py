@@ -190,6 +190,25 @@ class PublicKey:
         return self._resident_call([self._ct(x), (flat, ew)], len(rows), lambda L, h, out:
                                    L.pgpu_batch_ct_matvec(self._h, h[0], h[1], len(rows), int(e_bits), out))
 
+    def matvec_bucket(self, x, w, e_bits=None):
+        """The encrypted matrix-vector product of ``matvec`` by the bucket method: the same arguments, the same result
+        bit for bit, for few rows over very many columns or weights of any width (a signed weight as w mod n).  One
+        pgpu_batch_ct_matvec_bucket call on a resident batch -- the weights stay on the host, which cuts their digits;
+        no window tables; there is no fall-back to ``matvec`` or to the element-wise route."""
+        rows = [list(r) for r in w] if len(w) and isinstance(w[0], (list, tuple)) else [list(w)]
+        cols = len(x)
+        if cols == 0 or not rows or any(len(r) != cols for r in rows):
+            raise RuntimeError("matvec error: Size mismatch!")
+        flat = [int(v) for r in rows for v in r]
+        if min(flat) < 0:
+            raise RuntimeError("matvec error: negative weights have no encoding (pass w mod n)")
+        if e_bits is None:
+            e_bits = max(1, max(v.bit_length() for v in flat))
+        ew = (int(e_bits) + 63) // 64
+        wa = ints_to_limbs([v & ((1 << (64 * ew)) - 1) for v in flat], ew)
+        return self._resident_call([self._ct(x)], len(rows), lambda L, h, out:
+                                   L.pgpu_batch_ct_matvec_bucket(self._h, h[0], _ptr(wa), ew, len(rows), int(e_bits), out))
+
     def matmul(self, x, w, transposed=False, e_bits=None):
         """Encrypted matrix product: x a list of n_vec lists of cols ciphertexts (ints modulo n^2), w a plaintext matrix
         (a list of rows of cols non-negative ints) -> a list of n_vec lists of rows ciphertexts, out[v][i] =
