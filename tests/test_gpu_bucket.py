@@ -2,7 +2,8 @@
     out[i] = prod_j x[j]^(w[i][j] mod 2^e_bits) mod n^2
 held bit-identical to Python's pow for the 1024-, 2048- and 3072-bit key classes: a shape whose level-1 chains fill more
 than one wavefront, forced windows and blocks (every path of the two reduction levels: level 1 alone, level 2 alone, both),
-the edge weights of tests/test_bucket_model.py, a full-width signed weight through CRT decrypt, the agreement with
+the same paths with more than 8192 chains under a 2048-bit key (the (4,18) form of the reductions beside the (8,9) one that
+small launches take), the edge weights of tests/test_bucket_model.py, a full-width signed weight through CRT decrypt, the agreement with
 pgpu_batch_ct_matvec, both input forms, chaining, two lanes at once, the refusals, the timing record and the Python
 layer.  Everything is exact: there are no tolerances.  In the reference such a map is composed from
 CipherText::operator* (ipcl/ciphertext.cpp:83-106) and operator+ (ciphertext.cpp:35-72) term by term."""
@@ -85,9 +86,84 @@ def edge_weights(e_bits, c, rng, count):
     return ws
 
 
+# ---- the reductions in the key's own (4,18) form: more than 8192 chains under a 2048-bit-class key ----
+WIDE_MAX_CHAINS = 8192                # policy::segsum_wide_pays(8, chains): ceil(chains / 8) <= kSimds = 1024 wavefronts
+BASE_COLS = 8
+# (c, b, e_bits, rows), and which form level 1 / level 2 must run in ("base": (4,18), "wide": (8,9), None: no such launch)
+BASE_SHAPES = {
+    1: ((2, 4, 61, 265), ("base", None)),     # level 1 alone: 8215 chains of length 4, nb = 1; W = 31, top window one bit
+    2: ((2, 1, 61, 265), (None, "base")),     # level 2 alone: 8215 chains of length 4, n_sqr = n_mul = 0
+    3: ((4, 4, 59, 547), ("base", "base")),   # 32820 and 8205 chains of length 4; W = 15, top window 3 bits, n_sqr 2, n_mul 4
+    4: ((8, 4, 49, 19), ("base", "wide")),    # 133 x 64 = 8512 chains of length 4, then 133 of length 64: one call, two forms
+}
+
+
+def reduce_chains(rows, e_bits, c, b):
+    """(W, [level 1, level 2]) with a level as (chains, length) or None, as pgpu_batch_ct_matvec_bucket launches them"""
+    W, nb = (e_bits + c - 1) // c, (1 << c) // b
+    return W, [(rows * W * nb, b) if b > 1 else None, (rows * W, nb) if nb > 1 else None]
+
+
+def wide_pays(L, bits, chains):
+    """the policy's own word on a launch of this many chains (pack_wide_pays is segsum_wide_pays while PGPU_PACK_WIDE is unset)"""
+    lanes, limbs = ctypes.c_int(), ctypes.c_int()
+    assert L.pgpu_ct_pack_plan(bits, chains, 3, 11, ctypes.byref(lanes), ctypes.byref(limbs), None) == 0
+    assert (lanes.value, limbs.value) in ((4, 18), (8, 9))
+    return lanes.value == 8
+
+
+def cyclic_weights(rows, cols, e_bits, c, rng):
+    """many output rows for the price of eight references: seven non-zero weight rows that hold every edge weight of
+    edge_weights() and random ones, and the all-zero row.  The rows of the call cycle through five of the eight -- five is
+    coprime to the 16 chains of a wavefront, so that every position in a wavefront meets every one of them --; row 0, the
+    middle row and the last row each have a weight row that no other row has.  Returns (table, pick): the distinct weight
+    rows and the number of the one that row i uses"""
+    ws = edge_weights(e_bits, c, rng, 7 * cols)
+    assert len(ws) == 7 * cols, "every edge weight must find a place"
+    t = [ws[k * cols:(k + 1) * cols] for k in range(7)]
+    table = [t[0], [0] * cols, t[1], t[2], t[3], t[4], t[5], t[6]]
+    pick = [i % 5 for i in range(rows)]
+    pick[0], pick[rows // 2], pick[rows - 1] = 5, 6, 7
+    return table, pick
+
+
+def base_form_shape(L, R, key, bits, nsq, x, xv, shape, rng):
+    """one of BASE_SHAPES on the resident x (its values xv), with PGPU_BUCKET_WINDOW / _BLOCK forced to the shape's (c, b)
+    by the caller: the plan is the shape's, every reduction level is on its side of the threshold -- by the count and by
+    the policy's own answer --, the call's rows equal pow().  Returns (y, table, pick)"""
+    (c, b, e_bits, rows), sides = BASE_SHAPES[shape]
+    cols = len(xv)
+    pc, pb, nbytes = plan(L, bits, rows, cols, e_bits)[:3]
+    assert (pc, pb) == (c, b)
+    W, levels = reduce_chains(rows, e_bits, pc, pb)
+    assert nbytes == rows * W * (1 << c) * 576 <= 80 << 20
+    for lv, side in zip(levels, sides):
+        assert (lv is None) == (side is None), (shape, lv, side)
+        if lv:
+            chains, length = lv
+            print("shape", shape, "chains", chains, "of length", length, side)
+            assert (chains <= WIDE_MAX_CHAINS) == (side == "wide") == wide_pays(L, bits, chains), (shape, chains)
+            assert length >= 4                                                   # the main loop iterates
+            if shape != 4:
+                assert chains % 16                                               # the last wavefront has idle groups
+    assert levels[1] is None or levels[1][0] % 8                                 # ... also in the wide form
+    table, pick = cyclic_weights(rows, cols, e_bits, c, rng)
+    assert len({tuple(r) for r in table}) == 8 and all(pick.count(k) == 1 for k in (5, 6, 7)) and table[1] == [0] * cols
+    w = [v for i in range(rows) for v in table[pick[i]]]
+    y = bucket(L, R, key, x, w, rows, e_bits, words=(e_bits + 3) // 64 + 1)      # (room for the bits above e_bits)
+    assert L.pgpu_batch_count(y) == rows and L.pgpu_batch_row_limbs(y) == 144
+    want = [expect(xv, r, 1, e_bits, nsq)[0] for r in table]                     # once per distinct weight row
+    assert want[1] == 1 and len(set(want)) == 8
+    got = R.down(y)
+    bad = [i for i in range(rows) if got[i] != want[pick[i]]]
+    assert not bad, (shape, len(bad), bad[:20])
+    return y, table, pick
+
+
 @pytest.fixture
 def knobs(monkeypatch):
     names = ("PGPU_BUCKET_WINDOW", "PGPU_BUCKET_BLOCK", "PGPU_SEGSUM_CHUNK")
+    monkeypatch.delenv("PGPU_PACK_WIDE", raising=False)           # (wide_pays asks the pack plan for the policy's threshold)
     for name in names:
         monkeypatch.delenv(name, raising=False)
 
@@ -149,6 +225,43 @@ def test_forced_plans(engine, knobs, bits):
                     knobs(cw, b)
                     assert plan(L, bits, 2, 40, e_bits)[:2] == (cw, b)
                     assert R.down(bucket(L, R, c.pk._h, x, w, 2, e_bits)) == want, (e_bits, cw, b)
+    finally:
+        R.close()
+
+
+@pytest.mark.parametrize("shape", sorted(BASE_SHAPES))
+def test_reductions_in_the_base_form(engine, knobs, shape):
+    """bucket_reduce_kernel has four instantiations (k_hensel.hip parts 63-66), and a 2048-bit-class key runs the reductions
+    of small calls in the wide one:
+      <2,19>  part 63  every test of this module at 1024 bits (the class has no wide form)
+      <8,14>  part 65  every test of this module at 3072 bits (likewise)
+      <8,9>   part 66  every test of this module at 2048 bits but this one -- none of their launches has more than 8192
+                       chains --, and level 2 of shape 4 here
+      <4,18>  part 64  this test (shapes 1-4 of BASE_SHAPES), test_launches_of_one_call_in_two_forms, and
+                       test_gpu_key_widths.py::test_bucket_reductions_in_both_forms at the first and the last width of the class
+    Each shape derives its chain counts from the plan's (c, b) and asserts on which side of the threshold every level
+    falls (base_form_shape); the counts leave idle groups in the last wavefront, except level 1 of shape 4 (8512 = 532 x 16).
+    The accumulation levels of these shapes run in (4,18) as well, the Horner launch over the rows in (8,9).  x is
+    uploaded words with the ends of the value range in the first four columns; shape 1 runs a second time on pair rows
+    from a resident DJN encrypt and goes through CRT decrypt"""
+    c = Case(engine, 2048)
+    rng = random.Random(6400 + shape)
+    L, R = c.L, c.R
+    (cw, b, e_bits, _), _ = BASE_SHAPES[shape]
+    try:
+        knobs(cw, b)
+        xv = [1, c.nsq - 1, c.n + 1, c.nsq - c.n + 1] + [rng.randrange(1, c.nsq) for _ in range(BASE_COLS - 4)]
+        x = R.up(xv, 2 * c.nw)
+        base_form_shape(L, R, c.pk._h, 2048, c.nsq, x, xv, shape, rng)
+        assert R.down(x) == xv                                                   # the input is unchanged
+        if shape == 1:
+            m = [rng.randrange(c.n) for _ in range(BASE_COLS)]
+            xp = c.encrypt(m, rng)
+            assert L.pgpu_batch_row_limbs(xp) == 144
+            y, table, pick = base_form_shape(L, R, c.pk._h, 2048, c.nsq, xp, R.down(xp), shape, rng)
+            mask = (1 << e_bits) - 1
+            plain = [sum((w & mask) * v for w, v in zip(r, m)) % c.n for r in table]
+            assert R.down(R.op(L.pgpu_batch_decrypt_crt, c.sk._h, y)) == [plain[k] for k in pick]
     finally:
         R.close()
 
@@ -406,6 +519,41 @@ def test_launches_carry_the_bucket_kind(engine, knobs):
                 assert R.down(y) == expect(xv, w, rows, e_bits, c.nsq)
         finally:
             L.pgpu_set_timing(0)
+    finally:
+        R.close()
+
+
+def test_launches_of_one_call_in_two_forms(engine, knobs):
+    """shape 4 of BASE_SHAPES: level 1 in (4,18), level 2 in (8,9) within one call.  A bucket holds at most the 8 columns, so
+    chunk 64 gives one accumulation level: 1 + 2 reduces + the Horner launch, every one -- the base-form one included --
+    recorded once, with kind 12 and form PGPU_FORM_SEQ"""
+    c = Case(engine, 2048)
+    rng = random.Random(13)
+    L, R = c.L, c.R
+    (cw, b, e_bits, rows), sides = BASE_SHAPES[4]
+    try:
+        x = c.encrypt([rng.randrange(c.n) for _ in range(BASE_COLS)], rng)       # pair rows: no conversion launch
+        xv = R.down(x)
+        knobs(cw, b, 64)
+        W, levels = reduce_chains(rows, e_bits, *plan(L, 2048, rows, BASE_COLS, e_bits)[:2])
+        assert W > 1 and sides == ("base", "wide")
+        assert [wide_pays(L, 2048, lv[0]) for lv in levels] == [False, True]
+        table, pick = cyclic_weights(rows, BASE_COLS, e_bits, cw, rng)
+        w = [v for i in range(rows) for v in table[pick[i]]]
+        kinds, forms, ms = (ctypes.c_int * 64)(), (ctypes.c_int * 64)(), (ctypes.c_double * 64)()
+        assert L.pgpu_set_timing(1) == 0
+        try:
+            assert L.pgpu_synchronize() == 0
+            L.pgpu_timing_collect_ex(kinds, forms, ms, 64)                       # drop what the set-up left
+            y = bucket(L, R, c.pk._h, x, w, rows, e_bits)
+            assert L.pgpu_synchronize() == 0
+            n = L.pgpu_timing_collect_ex(kinds, forms, ms, 64)                   # (before the download, which may launch a conversion)
+            assert n == 1 + 2 + 1, n
+            assert all(kinds[i] == KIND_BUCKET and forms[i] == FORM_SEQ and ms[i] > 0 for i in range(n))
+        finally:
+            L.pgpu_set_timing(0)
+        want = [expect(xv, r, 1, e_bits, c.nsq)[0] for r in table]
+        assert R.down(y) == [want[k] for k in pick]
     finally:
         R.close()
 

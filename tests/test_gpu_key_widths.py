@@ -7,9 +7,12 @@ decrypt pchunks / pchunk_limbs / kappa, the R^2 2^(64 cw i) ladders of capi_keys
 that is exercised by the tests of the standard sizes.
 
 Everything is compared bit for bit with Python integers (pow, %) and the Python oracle: encrypt (DJN and r^n), CT+CT,
-CT x PT, CT+PT, CRT decrypt in every form a key has, matvec, segment_sum, segment_scan and pack, with edge plaintexts,
-randomness, exponents and ciphertext values, at batch sizes 1 and 37 (ragged for 16, 8 and 4 elements per wavefront).
-The reference takes any key length that is a multiple of 4 (ipcl/keygen.cpp:101) and composes all of these from
+CT x PT, CT+PT, CRT decrypt in every form a key has, matvec, segment_sum, segment_scan, pack, spmv, matmul (both layouts)
+and the bucket matvec, with edge plaintexts, randomness, exponents, weights and ciphertext values, at batch sizes 1 and 37
+(ragged for 16, 8 and 4 elements per wavefront).  Keys of the (4,18) class run their aggregation kernels in two forms,
+(4,18) and (8,9) by the size of the launch: pack and segment_sum are run in both at four widths of that class, the bucket
+reduction at its first and its last (the weighted sum has its own widths test in test_gpu_wsum.py).  One bit beyond the last class every
+aggregation call and its plan query refuses.  The reference takes any key length that is a multiple of 4 (ipcl/keygen.cpp:101) and composes all of these from
 PublicKey::encrypt (pub_key.cpp:82-129), CipherText::operator+ / operator* (ciphertext.cpp:35-106) and
 PrivateKey::decrypt (pri_key.cpp:65-157)."""
 import ctypes
@@ -28,6 +31,7 @@ GOLD = os.path.join(os.path.dirname(__file__), "golden")
 NONE = 0xFFFFFFFF                                    # kSegsumNone
 UNSUPPORTED = -3                                     # PGPU_ERR_UNSUPPORTED
 REVERSE = 1                                          # PGPU_SCAN_REVERSE
+MATMUL_TRANSPOSED = 1                                # PGPU_MATMUL_TRANSPOSED
 COUNTS = (1, 37)
 
 
@@ -150,7 +154,9 @@ def _half_limbs(form):
 
 @pytest.fixture(autouse=True)
 def knobs(monkeypatch):
-    names = ("PGPU_MATVEC_SLICES", "PGPU_MATVEC_WINDOW", "PGPU_SEGSUM_CHUNK", "PGPU_SEGSCAN_CHUNK", "PGPU_PACK_WIDE")
+    names = ("PGPU_MATVEC_SLICES", "PGPU_MATVEC_WINDOW", "PGPU_SEGSUM_CHUNK", "PGPU_SEGSCAN_CHUNK", "PGPU_PACK_WIDE",
+             "PGPU_SPMV_WINDOW", "PGPU_SPMV_CHUNK", "PGPU_MATMUL_WINDOW", "PGPU_MATMUL_TILE", "PGPU_MATMUL_SLICES",
+             "PGPU_BUCKET_WINDOW", "PGPU_BUCKET_BLOCK")
     for name in names:
         monkeypatch.delenv(name, raising=False)
 
@@ -607,6 +613,180 @@ def test_pack_at_the_capacity_bound(engine, knobs, bits):
         K.close()
 
 
+def _edge_matrix(rng, rows, cols):
+    """32-bit weights with 0, 1 and 2^32 - 1, an all-zero and an all-ones row (rows >= 3, cols >= 3)"""
+    wm = [[rng.getrandbits(32) for _ in range(cols)] for _ in range(rows)]
+    wm[0][:3] = [0, 1, (1 << 32) - 1]
+    wm[1] = [0] * cols
+    wm[2] = [(1 << 32) - 1] * cols
+    return wm
+
+
+def _spmv(K, x, row_ptr, col_idx, wb, e_bits):
+    rp, ci = np.array(row_ptr, dtype=np.uint64), np.array(col_idx, dtype=np.uint32)
+    return K.R.op(K.L.pgpu_batch_ct_spmv, K.pk._h, x, rp.ctypes.data_as(ctypes.c_void_p), ci.ctypes.data_as(ctypes.c_void_p),
+                  wb, len(row_ptr) - 1, e_bits)
+
+
+def _spmv_expect(K, xs, row_ptr, col_idx, weights):
+    out = []
+    for i in range(len(row_ptr) - 1):
+        acc = 1
+        for t in range(row_ptr[i], row_ptr[i + 1]):
+            acc = acc * pow(xs[col_idx[t]], weights[t], K.nsq) % K.nsq
+        out.append(acc)
+    return out
+
+
+@pytest.mark.parametrize("bits", PAIR_WIDTHS)
+def test_spmv(engine, knobs, bits):
+    """5 rows over 7 columns: a full row, an empty one, one of a single entry; with the default chunk and with chunk 2 (the
+    rows of 7 and 4 entries are cut into chains and folded)"""
+    K = Key(engine, bits)
+    L, R = K.L, K.R
+    rng = random.Random(bits + 10)
+    cols = 7
+    try:
+        x, m = K.fresh(rng, cols)
+        xs = R.down(x)
+        row_ptr, col_idx = [0], []
+        for length in (3, 0, 1, 7, 4):
+            col_idx += rng.sample(range(cols), length)                          # (unsorted within a row)
+            row_ptr.append(len(col_idx))
+        weights = [rng.getrandbits(32) for _ in col_idx]
+        weights[:3] = [0, 1, (1 << 32) - 1]
+        weights[3] = (1 << 32) - 1                                               # the row of one entry
+        weights[4:6] = [(1 << 32) - 1, 0]
+        want = _spmv_expect(K, xs, row_ptr, col_idx, weights)
+        assert want[1] == 1
+        plain = [sum(weights[t] * m[col_idx[t]] for t in range(row_ptr[i], row_ptr[i + 1])) % K.n for i in range(5)]
+        wb = R.up(weights, 1)
+        chunk, levels = ctypes.c_int(), ctypes.c_int()
+        for forced in (None, 2):
+            knobs(spmv_chunk=forced)
+            assert L.pgpu_ct_spmv_plan(bits, 5, cols, len(col_idx), 7, 32, None, ctypes.byref(chunk), ctypes.byref(levels), None, None) == 0
+            if forced:
+                assert chunk.value == 2 and levels.value > 1                     # fold levels exist
+            y = _spmv(K, x, row_ptr, col_idx, wb, 32)
+            assert L.pgpu_batch_count(y) == 5 and L.pgpu_batch_row_limbs(y) == 2 * K.l2
+            assert R.down(y) == want, forced
+            assert K.decrypt(y) == plain, forced
+            edge = [1, K.nsq - 1, K.n + 1] + xs[3:]                              # word rows with the ends of the range
+            assert R.down(_spmv(K, R.up(edge, 2 * K.nw), row_ptr, col_idx, wb, 32)) == _spmv_expect(K, edge, row_ptr, col_idx, weights), forced
+    finally:
+        K.close()
+
+
+def _transpose(flat, outer, inner):
+    """[outer][inner] -> [inner][outer]"""
+    return [flat[a * inner + b] for b in range(inner) for a in range(outer)]
+
+
+@pytest.mark.parametrize("bits", PAIR_WIDTHS)
+def test_matmul(engine, knobs, bits):
+    """3 vectors of 7 under a 5 x 7 matrix, in both layouts: with the plan's knobs, and with tiles of 2 vectors (a last pass
+    of one; the transposed layout staged) over 3 column slices (folded)"""
+    K = Key(engine, bits)
+    L, R = K.L, K.R
+    rng = random.Random(bits + 11)
+    n_vec, rows, cols = 3, 5, 7
+    try:
+        x, m = K.fresh(rng, n_vec * cols)
+        xs = R.down(x)
+        xt = R.up(_transpose(xs, n_vec, cols), 2 * K.nw)                         # the same matrix of ciphertexts stored [cols][n_vec]
+        wm = _edge_matrix(rng, rows, cols)
+        want = [v for k in range(n_vec) for v in _matvec_expect(K, xs[k * cols:(k + 1) * cols], wm)]
+        assert [want[k * rows + 1] for k in range(n_vec)] == [1] * n_vec
+        plain = [sum(a * w for a, w in zip(m[k * cols:(k + 1) * cols], row)) % K.n for k in range(n_vec) for row in wm]
+        wb = R.up([v for row in wm for v in row], 1)
+        sl, tile = ctypes.c_int(), ctypes.c_size_t()
+        for forced in (None, (3, 2)):
+            knobs(matmul_slices=forced and forced[0], matmul_tile=forced and forced[1])
+            assert L.pgpu_ct_matmul_plan(bits, n_vec, rows, cols, 32, None, ctypes.byref(sl), ctypes.byref(tile), None, None) == 0
+            if forced:
+                assert (sl.value, tile.value) == forced and tile.value < n_vec
+            y = R.op(L.pgpu_batch_ct_matmul, K.pk._h, x, wb, n_vec, rows, 32, 0)
+            assert L.pgpu_batch_count(y) == n_vec * rows and L.pgpu_batch_row_limbs(y) == 2 * K.l2
+            assert R.down(y) == want, forced
+            assert K.decrypt(y) == plain, forced
+            yt = R.op(L.pgpu_batch_ct_matmul, K.pk._h, xt, wb, n_vec, rows, 32, MATMUL_TRANSPOSED)
+            assert L.pgpu_batch_count(yt) == n_vec * rows and L.pgpu_batch_row_limbs(yt) == 2 * K.l2
+            assert R.down(yt) == _transpose(want, n_vec, rows), forced
+            assert K.decrypt(yt) == _transpose(plain, n_vec, rows), forced
+    finally:
+        K.close()
+
+
+def _bucket(K, x, weights, rows, e_bits):
+    ww = (e_bits + 63) // 64
+    wa = K.R.i2l(weights, ww)
+    return K.R.op(K.L.pgpu_batch_ct_matvec_bucket, K.pk._h, x, wa.ctypes.data_as(ctypes.c_void_p), ww, rows, e_bits)
+
+
+@pytest.mark.parametrize("bits", PAIR_WIDTHS)
+def test_matvec_bucket(engine, knobs, bits):
+    """2 x 40 under forced (c, b): both reduction levels, level 2 alone, level 1 alone; 13-bit weights and 65-bit ones in two
+    words.  x once as pair rows from a resident encrypt (and through CRT decrypt), once as uploaded words with the ends of
+    the value range in the first columns; the dense matvec on the same x and weights gives the same rows"""
+    K = Key(engine, bits)
+    L, R = K.L, K.R
+    rng = random.Random(bits + 12)
+    rows, cols = 2, 40
+    c, b = ctypes.c_int(), ctypes.c_int()
+    try:
+        x, m = K.fresh(rng, cols)
+        xs = R.down(x)
+        edge = [1, K.nsq - 1, K.n + 1, K.nsq - K.n + 1] + xs[4:]
+        xe = R.up(edge, 2 * K.nw)
+        for e_bits in (13, 65):
+            w = [rng.getrandbits(e_bits) for _ in range(rows * cols)]
+            w[:3] = [0, 1, (1 << e_bits) - 1]
+            wm = [w[i * cols:(i + 1) * cols] for i in range(rows)]
+            tail = _matvec_expect(K, xs[4:], [r[4:] for r in wm])                # the columns both inputs share: once
+            want = [a * b4 % K.nsq for a, b4 in zip(tail, _matvec_expect(K, xs[:4], [r[:4] for r in wm]))]
+            want_e = [a * b4 % K.nsq for a, b4 in zip(tail, _matvec_expect(K, edge[:4], [r[:4] for r in wm]))]
+            plain = [sum(a * v for a, v in zip(m, r)) % K.n for r in wm]
+            wb = R.up(w, (e_bits + 63) // 64)
+            assert R.down(R.op(L.pgpu_batch_ct_matvec, K.pk._h, x, wb, rows, e_bits)) == want
+            assert R.down(R.op(L.pgpu_batch_ct_matvec, K.pk._h, xe, wb, rows, e_bits)) == want_e
+            for cw, blk in ((4, 4), (3, 1), (3, 8)):
+                knobs(bucket_window=cw, bucket_block=blk)
+                assert L.pgpu_ct_matvec_bucket_plan(bits, rows, cols, e_bits, ctypes.byref(c), ctypes.byref(b), None, None, None) == 0
+                assert (c.value, b.value) == (cw, blk)
+                y = _bucket(K, x, w, rows, e_bits)
+                assert L.pgpu_batch_count(y) == rows and L.pgpu_batch_row_limbs(y) == 2 * K.l2
+                assert R.down(y) == want, (e_bits, cw, blk)
+                assert K.decrypt(y) == plain, (e_bits, cw, blk)
+                assert R.down(_bucket(K, xe, w, rows, e_bits)) == want_e, (e_bits, cw, blk)
+            knobs()
+    finally:
+        K.close()
+
+
+@pytest.mark.parametrize("bits", [WIDE_WIDTHS[0], WIDE_WIDTHS[-1]])
+def test_bucket_reductions_in_both_forms(engine, knobs, bits):
+    """the first and the last width of the (4,18) class -- at the last one R = 2^8 P and no more, and the bucket reduction is
+    lazily reduced end to end --: shape 3 of test_gpu_bucket.BASE_SHAPES puts both reduction levels beyond 8192 chains, on
+    bucket_reduce_kernel<4,18>; its first two rows alone are a small call, on <8,9> as in test_matvec_bucket, and give the
+    same rows"""
+    import test_gpu_bucket as tb
+    K = Key(engine, bits)
+    L, R = K.L, K.R
+    rng = random.Random(bits + 13)
+    (cw, blk, e_bits, rows), _ = tb.BASE_SHAPES[3]
+    try:
+        knobs(bucket_window=cw, bucket_block=blk)
+        xv = [1, K.nsq - 1, K.n + 1, K.nsq - K.n + 1] + [rng.randrange(1, K.nsq) for _ in range(tb.BASE_COLS - 4)]
+        x = R.up(xv, 2 * K.nw)
+        y, table, pick = tb.base_form_shape(L, R, K.pk._h, bits, K.nsq, x, xv, 3, rng)
+        W, levels = tb.reduce_chains(2, e_bits, cw, blk)
+        assert all(tb.wide_pays(L, bits, lv[0]) for lv in levels)
+        small = _bucket(K, x, table[pick[0]] + table[pick[1]], 2, e_bits)
+        assert R.down(small) == R.down(y)[:2]
+    finally:
+        K.close()
+
+
 @pytest.mark.parametrize("bits", WIDE_WIDTHS)
 def test_base_and_wide_forms_agree(engine, knobs, bits):
     """keys of the (4,18) class run small launches of segment_sum and pack on 8 lanes per half with 9 limbs each: both
@@ -653,7 +833,8 @@ def test_base_and_wide_forms_agree(engine, knobs, bits):
 # ---------------------------------------------------------------------------------------------------------------------
 def test_keys_without_a_pair_form_refuse_the_aggregations(engine, knobs):
     """3212 bits: one bit beyond (8,14).  The element-wise chain runs on word rows (test_resident_chain); matvec,
-    segment_sum, segment_scan and pack return PGPU_ERR_UNSUPPORTED before anything is launched, and so do their plans"""
+    segment_sum, segment_scan, pack, spmv, matmul and the bucket matvec return PGPU_ERR_UNSUPPORTED before anything is
+    launched, and so do their plans"""
     K = Key(engine, 3212)
     L, R = K.L, K.R
     rng = random.Random(3212)
@@ -662,6 +843,8 @@ def test_keys_without_a_pair_form_refuse_the_aggregations(engine, knobs):
         x = R.up(xs, 2 * K.nw)
         w = R.up([1, 2, 3, 4, 5, 6], 1)
         ids = np.zeros(6, dtype=np.uint32)
+        row_ptr, col_idx = np.array([0, 3, 6], dtype=np.uint64), np.arange(6, dtype=np.uint32)
+        wh = R.i2l([1, 2, 3, 4, 5, 6], 1)                                        # host weights of the bucket matvec
         out = ctypes.c_void_p()
         assert L.pgpu_set_timing(1) == 0
         try:
@@ -671,6 +854,16 @@ def test_keys_without_a_pair_form_refuse_the_aggregations(engine, knobs):
             assert L.pgpu_batch_ct_segment_sum(K.pk._h, x, ids.ctypes.data_as(ctypes.c_void_p), 1, 2, ctypes.byref(out)) == UNSUPPORTED
             assert L.pgpu_batch_ct_segment_scan(K.pk._h, x, 3, 0, ctypes.byref(out)) == UNSUPPORTED
             assert L.pgpu_batch_ct_pack(K.pk._h, x, 3, 5, ctypes.byref(out)) == UNSUPPORTED
+            assert not out.value
+            assert L.pgpu_batch_ct_spmv(K.pk._h, x, row_ptr.ctypes.data_as(ctypes.c_void_p), col_idx.ctypes.data_as(ctypes.c_void_p),
+                                        w, 2, 32, ctypes.byref(out)) == UNSUPPORTED
+            assert b"pair" in L.pgpu_last_error() and not out.value
+            for flags in (0, MATMUL_TRANSPOSED):                                 # 2 vectors of 3 under a 2 x 3 matrix
+                assert L.pgpu_batch_ct_matmul(K.pk._h, x, w, 2, 2, 32, flags, ctypes.byref(out)) == UNSUPPORTED
+                assert b"pair" in L.pgpu_last_error() and not out.value
+            assert L.pgpu_batch_ct_matvec_bucket(K.pk._h, x, wh.ctypes.data_as(ctypes.c_void_p), 1, 1, 32, ctypes.byref(out)) == UNSUPPORTED
+            assert b"pair" in L.pgpu_last_error() and not out.value
+            assert L.pgpu_synchronize() == 0
             assert L.pgpu_timing_collect_ex(kinds, forms, ms, 64) == 0 and not out.value
         finally:
             L.pgpu_set_timing(0)
@@ -679,6 +872,11 @@ def test_keys_without_a_pair_form_refuse_the_aggregations(engine, knobs):
         assert L.pgpu_ct_segment_sum_plan(3212, 6, 2, 6, ctypes.byref(a), ctypes.byref(b)) == UNSUPPORTED
         assert L.pgpu_ct_segment_scan_plan(3212, 2, 3, ctypes.byref(a), ctypes.byref(b), ctypes.byref(pr)) == UNSUPPORTED
         assert L.pgpu_ct_pack_plan(3212, 2, 3, 5, ctypes.byref(a), ctypes.byref(b), ctypes.byref(pr)) == UNSUPPORTED
+        lv, tile = ctypes.c_int(), ctypes.c_size_t()
+        assert L.pgpu_ct_spmv_plan(3212, 2, 6, 6, 3, 32, ctypes.byref(a), ctypes.byref(b), ctypes.byref(lv), ctypes.byref(pr), None) == UNSUPPORTED
+        assert L.pgpu_ct_matmul_plan(3212, 2, 2, 3, 32, ctypes.byref(a), ctypes.byref(b), ctypes.byref(tile), ctypes.byref(pr), None) == UNSUPPORTED
+        assert L.pgpu_ct_matvec_bucket_plan(3212, 1, 6, 32, ctypes.byref(a), ctypes.byref(b), ctypes.byref(pr), None, None) == UNSUPPORTED
+        assert b"pair" in L.pgpu_last_error()
         # ... and the same values still add, multiply and decrypt on word rows
         s = R.op(L.pgpu_batch_ct_add, K.pk._h, x, x)
         assert L.pgpu_batch_row_limbs(s) == 2 * K.l2 and R.down(s) == [v * v % K.nsq for v in xs]
