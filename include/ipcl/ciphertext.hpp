@@ -20,6 +20,8 @@ CipherText sparseMatVec(const std::vector<uint64_t>& row_ptr, const std::vector<
                         const CipherText& x);
 CipherText weightedSum(const std::vector<CipherText>& xs, const PlainText& w);
 CipherText sum(const std::vector<CipherText>& xs);
+struct Conv2dShape;   // include/ipcl/ext/conv.hpp
+CipherText conv2d(const PlainText& w, const CipherText& x, const Conv2dShape& shape);
 // include/ipcl/ext/aggregate.hpp
 CipherText segmentSum(const CipherText& x, const std::vector<uint32_t>& ids, std::size_t n_segments, std::size_t groups);
 CipherText segmentScan(const CipherText& x, std::size_t seg_len, bool reverse);
@@ -66,6 +68,9 @@ class CipherText : public BaseText {
   friend CipherText ext::sum(const std::vector<CipherText>& xs);
   // prod_k xs[k][i]^w[k] (w == null: every weight 1), one weight per CipherText: csrc/host/linear.cpp
   static CipherText weightedSumMap(const std::vector<CipherText>& xs, const PlainText* w);
+  friend CipherText ext::conv2d(const PlainText& w, const CipherText& x, const ext::Conv2dShape& shape);
+  // prod_{ci,ky,kx} this(n, ci, oy*sh + ky - ph, ox*sw + kx - pw)^w[co][ci][ky][kx]: csrc/host/conv.cpp
+  CipherText convMap(const PlainText& w, const ext::Conv2dShape& shape) const;
   friend CipherText ext::segmentSum(const CipherText& x, const std::vector<uint32_t>& ids, std::size_t n_segments,
                                     std::size_t groups);
   // prod_{j: ids[g][j] == s} this[j]: csrc/host/aggregate.cpp

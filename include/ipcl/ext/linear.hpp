@@ -20,7 +20,8 @@
 //                        the same map with the plaintext matrix in CSR form, rows = row_ptr.size() - 1:
 //                        Y[i] = prod_{ row_ptr[i] <= t < row_ptr[i+1] } X[col_idx[t]]^w[t] mod n^2 -- a neighbourhood
 //                        aggregation over a graph, a sparse or pruned layer, a convolution as a banded matrix, a weighted
-//                        group-by.  w holds the row_ptr.back() weights in CSR order.  Entries of a row need not be sorted, a
+//                        group-by (a convolution proper has its own call: ipcl/ext/conv.hpp, conv2d -- no index list, no
+//                        replicated weights, the images walked in tiles).  w holds the row_ptr.back() weights in CSR order.  Entries of a row need not be sorted, a
 //                        column named twice contributes twice, an empty row yields an encryption of 0 (the ciphertext 1).
 //                        One pgpu_batch_ct_spmv call: the window tables of the x[j] shared by all rows, the squarings
 //                        shared by the terms of a chain of a row.

@@ -397,7 +397,7 @@ int pgpu_batch_ct_pack(const pgpu_pubkey* key, const pgpu_batch* x, size_t seg_l
  * count beyond size_t.  PGPU_ERR_UNSUPPORTED: no pair rows for keys of key_bits. */
 int pgpu_ct_pack_plan(int key_bits, size_t rows, size_t seg_len, int slot_bits, int* lanes, int* limbs, size_t* products);
 /* Encrypted sparse matrix-vector product (a neighbourhood aggregation over a graph, a sparse or pruned linear layer, a
- * convolution as a banded matrix, SUM(v*x) GROUP BY id): x a resident ciphertext batch of cols = pgpu_batch_count(x)
+ * convolution as a banded matrix -- pgpu_batch_ct_conv2d below does that without the index list --, SUM(v*x) GROUP BY id): x a resident ciphertext batch of cols = pgpu_batch_count(x)
  * elements (pair rows, or uploaded plain ciphertext words: converted on the way in), the plaintext matrix A in CSR form:
  * row_ptr[rows + 1] and col_idx[nnz] HOST arrays, w a plain uploaded batch of nnz = row_ptr[rows] exponents in CSR order,
  * each < 2^e_bits (bits at and above e_bits are ignored):
@@ -533,6 +533,49 @@ int pgpu_batch_ct_matvec_bucket(const pgpu_pubkey* key, const pgpu_batch* x, con
  * pair rows for keys of key_bits. */
 int pgpu_ct_matvec_bucket_plan(int key_bits, size_t rows, size_t cols, int e_bits, int* window, int* block,
                                size_t* bucket_bytes, size_t* products, size_t* depth);
+/* Encrypted 2-D convolution (a convolutional layer on encrypted images, a sliding-window or moving sum, sum pooling): x a
+ * resident ciphertext batch of n_img*c_in*h*w elements (pair rows, or uploaded plain ciphertext words: converted on the way
+ * in) read as [n_img][c_in][h][w]; w a plain uploaded batch of c_out*c_in*kh*kw exponents read as [c_out][c_in][kh][kw],
+ * each < 2^e_bits (bits at and above e_bits are ignored).  With
+ *     oh = (h + 2*pad_h - kh) / stride_h + 1 (floor),   ow likewise,
+ *     out[n][co][oy][ox] = prod_{ci,ky,kx} x[n][ci][oy*stride_h + ky - pad_h][ox*stride_w + kx - pad_w]^w[co][ci][ky][kx] mod n^2,
+ * a tap outside the image contributing 1 (zero padding): Dec(out) is the cross-correlation that
+ * torch.nn.functional.conv2d computes, taken mod n.  h == kh == 1 is a 1-D convolution; sum pooling is the caller's reshape
+ * (n_img' = n_img*c, c_in = c_out = 1, all-ones taps, e_bits = 1, stride equal to the kernel).  An all-zero filter yields the
+ * ciphertext 1; negative weights have no encoding (pass w mod n).  Not offered: dilation, groups, a bias (that is
+ * pgpu_batch_ct_add_plain on the result), and tiling inside one image.
+ * The schedule of an output is the matmul's; the images are walked in tiles of whole images -- one tile's window tables are
+ * built once, every tap of every output that reads a pixel addresses its table by arithmetic on the output position, and
+ * the table block is reused by the next tile ("Encrypted 2-D convolution"; what pgpu_batch_ct_spmv needs
+ * n_img*c_out*oh*ow*c_in*kh*kw column numbers and as many replicated weights for, and one table over all of x).  The
+ * result is an ordinary resident ciphertext batch of n_img*c_out*oh*ow elements in pair rows on the lane of x, laid out
+ * [n_img][c_out][oh][ow]: a second layer takes it as it is.  x is left unchanged.
+ * PGPU_ERR_INVALID_PARAM: null / stale handles, a dimension or stride equal to 0, pad_h >= kh or pad_w >= kw (a window that
+ * holds no element), kh > h + 2*pad_h or kw > w + 2*pad_w (no output), count(x) != n_img*c_in*h*w, count(w) !=
+ * c_out*c_in*kh*kw, w not a plain uploaded batch, e_bits < 1 or wider than the rows of w, ciphertext width mismatch, a batch
+ * of another key, a size product beyond size_t (an image or kernel side of 2^30 or more counts as one).
+ * PGPU_ERR_UNSUPPORTED: keys without pair rows (beyond 3072 bits; PGPU_PAIR_ROWS=0 / PGPU_HENSEL=0), pools of more than one
+ * GPU, and -- SIDE CHANNELS -- the masked table-gather policy: the tables are indexed by digits of the PLAINTEXT filters and
+ * by positions derived from the shape (never by key material or by anything encrypted).
+ * All refusals are decided on the host before any launch and leave *out untouched. */
+typedef struct pgpu_conv2d_shape {
+  size_t n_img, c_in, h, w, c_out, kh, kw, stride_h, stride_w, pad_h, pad_w;
+} pgpu_conv2d_shape;
+int pgpu_batch_ct_conv2d(const pgpu_pubkey* key, const pgpu_batch* x, const pgpu_batch* w, const pgpu_conv2d_shape* shape,
+                         int e_bits, pgpu_batch** out);
+/* What a call of this shape would run (host-side query, needs no device): the window width (1..6), the images of a tile
+ * (1..n_img; the call makes ceil(n_img / tile) passes, the last one over the images that remain), the tap slices of a full
+ * pass (1..c_in*kh*kw; a short last pass has the slices of its own size), the bytes of the table block (tile * c_in*h*w *
+ * 2^window pair rows) and the pair products of the whole call: per pass over t images, with n_o = c_out*oh*ow and taps =
+ * c_in*kh*kw, t*c_in*h*w*(2^w - 2) for the tables, t*n_o*S*e_bits squarings, t*n_o*taps*ceil(e_bits / w) products by table
+ * entries (padded taps counted: they are multiplied by one), t*n_o*(S - 1) for the fold.  Every pass is a table launch, a
+ * multiply launch and ceil(log2 S) fold launches.  The rule is policy.hpp: conv_plan; PGPU_CONV_WINDOW / PGPU_CONV_TILE /
+ * PGPU_CONV_SLICES force the three values, read at every call.
+ * PGPU_ERR_INVALID_PARAM: key_bits or e_bits < 1, a null shape, and what the call refuses of a shape alone: a dimension or
+ * stride equal to 0, pad >= kernel, kernel > padded image, a size product or a product count beyond size_t.
+ * PGPU_ERR_UNSUPPORTED: no pair rows for keys of key_bits. */
+int pgpu_ct_conv2d_plan(int key_bits, const pgpu_conv2d_shape* shape, int e_bits, int* window, int* slices, size_t* tile,
+                        size_t* table_bytes, size_t* products);
 
 /* ---- instrumentation used by bench.py (roofline) ----
  * With timing enabled every kernel launch is bracketed by two HIP events recorded on the stream
@@ -551,7 +594,8 @@ typedef enum pgpu_kernel_kind {
   PGPU_KERNEL_SPMV = 9,       /* every launch of pgpu_batch_ct_spmv: table build, multi-exponentiation, fold levels */
   PGPU_KERNEL_WSUM = 10,      /* every launch of pgpu_batch_ct_weighted_sum: the slices' schedules, the fold */
   PGPU_KERNEL_MATMUL = 11,    /* every launch of pgpu_batch_ct_matmul: per pass the table build, the multi-exponentiation, the fold */
-  PGPU_KERNEL_BUCKET = 12     /* every launch of pgpu_batch_ct_matvec_bucket: accumulation levels, bucket reductions, Horner */
+  PGPU_KERNEL_BUCKET = 12,    /* every launch of pgpu_batch_ct_matvec_bucket: accumulation levels, bucket reductions, Horner */
+  PGPU_KERNEL_CONV = 13       /* every launch of pgpu_batch_ct_conv2d: per pass the table build, the multi-exponentiation, the fold */
 } pgpu_kernel_kind;
 int pgpu_set_timing(int enabled);
 int pgpu_timing_collect(int* kinds, double* ms, int max_entries);

@@ -43,12 +43,19 @@ SYMBOLS = [
     "pgpu_batch_ct_spmv", "pgpu_ct_spmv_plan",
     "pgpu_batch_ct_weighted_sum", "pgpu_ct_weighted_sum_plan",
     "pgpu_batch_ct_matvec_bucket", "pgpu_ct_matvec_bucket_plan",
+    "pgpu_batch_ct_conv2d", "pgpu_ct_conv2d_plan",
 ]
 FEATURE_4096_SPLIT = 1
 SEGMENT_NONE = 0xFFFFFFFF      # PGPU_SEGMENT_NONE: the element is left out of that group
 SCAN_REVERSE = 1               # PGPU_SCAN_REVERSE: suffix instead of prefix products
 
 _lib = None
+
+
+class Conv2dShape(ctypes.Structure):
+    """pgpu_conv2d_shape"""
+    _fields_ = [(name, c_size_t) for name in ("n_img", "c_in", "h", "w", "c_out", "kh", "kw", "stride_h", "stride_w",
+                                              "pad_h", "pad_w")]
 
 
 class PgpuError(RuntimeError):
@@ -210,6 +217,11 @@ def lib():
     L.pgpu_ct_weighted_sum_plan.argtypes = [c_int, c_size_t, c_size_t, c_void_p, c_int, POINTER(c_int), POINTER(c_int),
                                             POINTER(c_int), POINTER(c_size_t), POINTER(c_size_t)]
     L.pgpu_ct_weighted_sum_plan.restype = c_int
+    L.pgpu_batch_ct_conv2d.argtypes = [c_void_p, c_void_p, c_void_p, POINTER(Conv2dShape), c_int, POINTER(c_void_p)]
+    L.pgpu_batch_ct_conv2d.restype = c_int
+    L.pgpu_ct_conv2d_plan.argtypes = [c_int, POINTER(Conv2dShape), c_int, POINTER(c_int), POINTER(c_int), POINTER(c_size_t),
+                                      POINTER(c_size_t), POINTER(c_size_t)]
+    L.pgpu_ct_conv2d_plan.restype = c_int
     _lib = L
     return L
 

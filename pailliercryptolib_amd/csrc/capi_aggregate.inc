@@ -1,4 +1,4 @@
-// pailliercryptolib_amd -- the aggregation calls on resident ciphertexts (pgpu_batch_ct_matvec / _matvec_bucket / _matmul / _spmv / _weighted_sum /
+// pailliercryptolib_amd -- the aggregation calls on resident ciphertexts (pgpu_batch_ct_matvec / _matvec_bucket / _matmul / _conv2d / _spmv / _weighted_sum /
 // _segment_sum / _segment_scan / _pack) and their plan queries (pgpu_ct_*_plan).
 // Part of the translation unit of capi.cpp (included there, in place, after capi_batches.inc, whose bounce buffer the plan
 // upload shares).  Every call is: its own parameter checks, the admission tail, its plan (policy.hpp), the result set-up,
@@ -326,6 +326,130 @@ int pgpu_batch_ct_matmul(const pgpu_pubkey* key, const pgpu_batch* x, const pgpu
     }
     if (S > 1 && staged)
       HIP_TRY(hipMemcpy2DAsync(dest, n_vec * row_bytes, partial.p, t * row_bytes, t * row_bytes, rows, hipMemcpyDeviceToDevice, r.s));
+  }
+  RC_TRY(lanes_order(w, r.x->lane, false));
+  return r.finish(out);
+}
+
+// ---- encrypted 2-D convolution (hensel_conv.hpp; policy.hpp: conv_*) ----
+static bool conv_dims(const pgpu_conv2d_shape* sh, policy::ConvDims* g) {
+  const size_t d[11] = {sh->n_img, sh->c_in, sh->h, sh->w, sh->c_out, sh->kh, sh->kw, sh->stride_h, sh->stride_w, sh->pad_h, sh->pad_w};
+  return policy::conv_geometry(d, g);
+}
+static const char* const kConvShapeMsg =
+    ": every dimension and stride must be positive, pad_h < kh, pad_w < kw, kh <= h + 2 pad_h, kw <= w + 2 pad_w, and no size "
+    "product may exceed size_t";
+
+int pgpu_ct_conv2d_plan(int key_bits, const pgpu_conv2d_shape* shape, int e_bits, int* window, int* slices, size_t* tile,
+                        size_t* table_bytes, size_t* products) {
+  if (key_bits < 1 || !shape || e_bits < 1) return fail(PGPU_ERR_INVALID_PARAM, "conv2d plan: key_bits and e_bits must be positive, the shape not null");
+  policy::ConvDims g{};
+  if (!conv_dims(shape, &g)) return fail(PGPU_ERR_INVALID_PARAM, std::string("conv2d plan") + kConvShapeMsg);
+  int G = 0, K = 0;
+  if (!policy::matvec_geometry(key_bits, &G, &K))
+    return fail(PGPU_ERR_UNSUPPORTED, "conv2d: keys of this size have no pair rows (1024- to 3072-bit key classes only)");
+  const size_t row_bytes = (size_t)2 * G * K * sizeof(uint32_t);
+  policy::ConvPlan plan;
+  policy::conv_plan(G, shape->n_img, g.elems, g.n_o, g.taps, e_bits, row_bytes, &plan);
+  if (plan.products >= 18446744073709551615.0) return fail(PGPU_ERR_INVALID_PARAM, "conv2d plan: the product count overflows");
+  if (window) *window = plan.window;
+  if (slices) *slices = (int)plan.slices;
+  if (tile) *tile = plan.tile;
+  if (table_bytes) *table_bytes = plan.tile * g.elems * ((size_t)1 << plan.window) * row_bytes;
+  if (products) *products = (size_t)plan.products;
+  return PGPU_OK;
+}
+
+int pgpu_batch_ct_conv2d(const pgpu_pubkey* key, const pgpu_batch* x, const pgpu_batch* w, const pgpu_conv2d_shape* shape,
+                         int e_bits, pgpu_batch** out) {
+  RC_TRY(rt::check_ready());
+  if (!key || !x || !w || !shape || !out) return fail(PGPU_ERR_INVALID_PARAM, "null argument");
+  RC_TRY(check_gen(key->gen, "key"));
+  RC_TRY(check_gen(x->gen, "batch"));
+  RC_TRY(check_gen(w->gen, "batch"));
+  policy::ConvDims g{};
+  if (!conv_dims(shape, &g)) return fail(PGPU_ERR_INVALID_PARAM, std::string("conv2d error") + kConvShapeMsg);
+  if (x->count != g.x_count) return fail(PGPU_ERR_INVALID_PARAM, "conv2d error: Size mismatch! (x must hold n_img * c_in * h * w ciphertexts)");
+  if (x->words != 2 * key->n_words) return fail(PGPU_ERR_INVALID_PARAM, "conv2d error: ciphertext width mismatch");
+  if (w->mont || w->pair_l2) return fail(PGPU_ERR_INVALID_PARAM, "conv2d error: the filters must be a plain uploaded batch");
+  if (w->count != g.w_count) return fail(PGPU_ERR_INVALID_PARAM, "conv2d error: Size mismatch! (the filters must hold c_out * c_in * kh * kw values)");
+  if (e_bits < 1 || e_bits > 64 * w->words) return fail(PGPU_ERR_INVALID_PARAM, "conv2d error: e_bits outside the rows of the filter batch");
+  // (pair rows of another key are reported in the words of the conversion, as_pair_batch, as for the matvec)
+  static const AggOp op{"conv2d", "images", " and this call indexes its window tables by digits of the plaintext filters and by positions "
+                                            "derived from the shape; no masked variant exists",
+                        pgpu::conv_has, "ciphertext batch belongs to a different key"};
+  const pgpu_pubkey::PubForm* pf = nullptr;
+  RC_TRY(agg_admit(op, key, &x, 1, &pf));
+  const int G = pf->H, K = pf->K;
+  const size_t LQ = (size_t)2 * G * K, row_bytes = LQ * sizeof(uint32_t);
+  policy::ConvPlan plan;
+  policy::conv_plan(G, shape->n_img, g.elems, g.n_o, g.taps, e_bits, row_bytes, &plan);
+  const int win = plan.window;
+  const size_t S_max = std::max(plan.slices, plan.last_slices);
+  AggRun r;
+  RC_TRY(r.open(key, pf, x, g.out_count));
+  RC_TRY(lanes_order(w, r.x->lane, true));
+  // one table block and one partial block for all passes: the block arena, on the lane's stream.  The images of a pass
+  // and their outputs are contiguous in x and in the result batch
+  rt::DevMem table, partial;
+  RC_TRY(table.alloc(*r.dev, r.s, plan.tile * g.elems * ((size_t)1 << win) * row_bytes));
+  if (S_max > 1) RC_TRY(partial.alloc(*r.dev, r.s, S_max * plan.tile * g.n_o * row_bytes));
+  for (size_t p = 0; p < plan.passes; ++p) {
+    const size_t i0 = p * plan.tile, t = p + 1 == plan.passes ? plan.last : plan.tile, n_out = t * g.n_o;
+    const size_t S = p + 1 == plan.passes ? plan.last_slices : plan.slices;
+    uint32_t* dest = r.o->prow(0) + i0 * g.n_o * LQ;
+    {
+      // the unchanged table build of the matvec over the tile: T[e][d] = x_e^d
+      pgpu::MatvecArgs ta{};
+      ta.ctx = hensel_pub_view(pf, r.dev->index);
+      ta.x = r.x->prow(0) + i0 * g.elems * LQ;
+      ta.table = (uint32_t*)table.p;
+      ta.window = win;
+      ta.cols = t * g.elems;
+      RC_TRY(timed_launch(r, t * g.elems, G, PGPU_KERNEL_CONV, "conv2d", [&](unsigned blocks) { return pgpu::launch_matvec_table(G, K, ta, blocks, r.s); }));
+    }
+    pgpu::ConvArgs a{};
+    a.ctx = hensel_pub_view(pf, r.dev->index);
+    a.table = (const uint32_t*)table.p;
+    a.wt = w->ptr(0);
+    a.w_stride = (size_t)w->words;
+    a.w_words = w->words;
+    a.e_bits = e_bits;
+    a.window = win;
+    a.slices = (int)S;
+    a.n_out = n_out;
+    a.c_in = (uint32_t)shape->c_in;       // (conv_geometry: every one of these below 2^31)
+    a.h = (uint32_t)shape->h;
+    a.w = (uint32_t)shape->w;
+    a.c_out = (uint32_t)shape->c_out;
+    a.kh = (uint32_t)shape->kh;
+    a.kw = (uint32_t)shape->kw;
+    // (a stride beyond the padded image leaves one output row or column: any such stride is as good as the smallest one)
+    a.sh = (uint32_t)std::min(shape->stride_h, shape->h + 2 * shape->pad_h);
+    a.sw = (uint32_t)std::min(shape->stride_w, shape->w + 2 * shape->pad_w);
+    a.ph = (uint32_t)shape->pad_h;
+    a.pw = (uint32_t)shape->pad_w;
+    a.oh = (uint32_t)g.oh;
+    a.ow = (uint32_t)g.ow;
+    a.out = S > 1 ? (uint32_t*)partial.p : dest;     // partial products [S][t][c_out][oh][ow], or straight into the result batch
+    a.o_slice_stride = S > 1 ? n_out : 0;
+    RC_TRY(timed_launch(r, n_out, G, PGPU_KERNEL_CONV, "conv2d", [&](unsigned blocks) { return pgpu::launch_conv(G, K, a, blocks, r.s); }, S));
+    // fold the S partial products of every output as the matvec does: ceil(log2 S) element-wise pair products over the
+    // slices, in place, the last one into the result batch
+    for (size_t cur = S; cur > 1;) {
+      const size_t h = (cur + 1) / 2;
+      pgpu::PairOpsArgs pa{};
+      pa.count = (cur - h) * n_out;
+      const pgpu_pubkey::PubForm* lf = pair_op_form(key, pf, pa.count);
+      pa.ctx = hensel_pub_view(lf, r.dev->index);
+      pa.op = pgpu::PO_MUL;
+      pa.a = (const uint32_t*)partial.p;
+      pa.b = (const uint32_t*)partial.p + h * n_out * LQ;
+      pa.b_stride = LQ;
+      pa.out = h == 1 ? dest : (uint32_t*)partial.p;
+      RC_TRY(pair_op_launch(*r.dev, lf, pa, r.s, PGPU_KERNEL_CONV));
+      cur = h;
+    }
   }
   RC_TRY(lanes_order(w, r.x->lane, false));
   return r.finish(out);

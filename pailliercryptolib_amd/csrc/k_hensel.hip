@@ -1,5 +1,5 @@
 // pailliercryptolib_amd -- instantiations of the split-form CRT-decrypt exponentiation (hensel.hpp), split over
-// PGPU_PART = 0..66 so that they compile in parallel (63-66: the bucket reduction of the bucket-method matvec; 60-62: the encrypted matrix product; 56-59: the encrypted weighted sum of K resident batches; 53-55: the encrypted sparse matrix-vector product; 38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 45-47: the encrypted segmented prefix sum; 48-51: the encrypted slot packing; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
+// PGPU_PART = 0..69 so that they compile in parallel (67-69: the encrypted 2-D convolution; 63-66: the bucket reduction of the bucket-method matvec; 60-62: the encrypted matrix product; 56-59: the encrypted weighted sum of K resident batches; 53-55: the encrypted sparse matrix-vector product; 38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 45-47: the encrypted segmented prefix sum; 48-51: the encrypted slot packing; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
 // the two-wavefronts-per-SIMD build of the (2,19) decrypt form; 11-13: element-wise operations on pair rows).
 #include "hensel_seq.hpp"
 #include "launch.hpp"
@@ -39,9 +39,12 @@
 #if defined(PGPU_PART) && PGPU_PART >= 63 && PGPU_PART <= 66
 #include "hensel_bucket.hpp"    // the bucket-method matvec: two running products per chain of buckets
 #endif
+#if defined(PGPU_PART) && PGPU_PART >= 67 && PGPU_PART <= 69
+#include "hensel_conv.hpp"      // the encrypted 2-D convolution: the matmul's schedule, table rows by arithmetic on the output position
+#endif
 
 #ifndef PGPU_PART
-#error "compile with -DPGPU_PART=0..66 (15 and 30 are retired)"
+#error "compile with -DPGPU_PART=0..69 (15 and 30 are retired)"
 #endif
 
 namespace pgpu {
@@ -653,6 +656,26 @@ bool PGPU_MM_NAME(int G, int K, const MatmulArgs& a, unsigned blocks, hipStream_
 bool PGPU_BK_NAME(int G, int K, const BucketArgs& a, unsigned blocks, hipStream_t s) {
   if (G != PGPU_BK_G || K != PGPU_BK_K) return false;
   hipLaunchKernelGGL((bucket_reduce_kernel<PGPU_BK_G, PGPU_BK_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
+  return true;
+}
+#elif PGPU_PART >= 67 && PGPU_PART <= 69
+// the encrypted 2-D convolution (hensel_conv.hpp): one geometry per part
+#if PGPU_PART == 67
+#define PGPU_CV_G 2
+#define PGPU_CV_K 19
+#define PGPU_CV_NAME launch_conv_part67
+#elif PGPU_PART == 68
+#define PGPU_CV_G 4
+#define PGPU_CV_K 18
+#define PGPU_CV_NAME launch_conv_part68
+#else
+#define PGPU_CV_G 8
+#define PGPU_CV_K 14
+#define PGPU_CV_NAME launch_conv_part69
+#endif
+bool PGPU_CV_NAME(int G, int K, const ConvArgs& a, unsigned blocks, hipStream_t s) {
+  if (G != PGPU_CV_G || K != PGPU_CV_K) return false;
+  hipLaunchKernelGGL((conv_kernel<PGPU_CV_G, PGPU_CV_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
   return true;
 }
 #else

@@ -441,6 +441,29 @@ struct MatmulArgs {
   size_t o_slice_stride, o_vec_stride, o_row_stride;   // in pair rows
 };
 
+// Encrypted 2-D convolution on pair rows (hensel_conv.hpp): one pass over a TILE of whole images,
+//     out(n, co, oy, ox) = prod_{ci, ky, kx} x(n, ci, oy*sh + ky - ph, ox*sw + kx - pw)^w[co][ci][ky][kx],
+// a tap outside the image contributing one.  The table is matvec_table_kernel's, built from MatvecArgs over the tile's
+// contiguous elements of x read as [images of the tile][c_in][h][w]: element (n, ci, iy, ix) is table row
+// ((n * c_in + ci) * h + iy) * w + ix.  Output o = ((n * c_out + co) * oh + oy) * ow + ox of tap slice s is row
+// s * o_slice_stride + o of `out` (the result batch at the tile's first output, or the partial block the fold reads).
+// No index list: every address follows from o and the shape.  The host keeps n_out = images of the tile * c_out * oh * ow,
+// oh = (h + 2 ph - kh) / sh + 1, ow likewise, ph < kh, pw < kw, and every dimension below 2^31.
+struct ConvArgs {
+  HenselPubDev ctx;
+  const uint32_t* table;     // [images of the tile * c_in * h * w][2^window][2*L2] T[e][d] = x_e^d
+  const uint64_t* wt;        // [c_out * c_in*kh*kw][w_stride] the plaintext filters, each value < 2^e_bits
+  size_t w_stride;
+  int w_words;               // valid words per value
+  int e_bits;                // >= 1
+  int window;                // 1..6
+  int slices;                // 1..c_in*kh*kw: ranges of the flat tap number with a partial product each
+  size_t n_out;              // >= 1: outputs are numbered flat over [images of the tile][c_out][oh][ow]
+  uint32_t c_in, h, w, c_out, kh, kw, sh, sw, ph, pw, oh, ow;
+  uint32_t* out;
+  size_t o_slice_stride;     // in pair rows
+};
+
 // Bucket reduction of the bucket-method matvec on pair rows (hensel_bucket.hpp): one chain per row of `src` read as
 // [chains][len], two running products walked from entry len - 1 down to entry 1,
 //     acc = prod_{i >= 1} src[i],   tot = prod_{i >= 1} src[i]^i        (2 (len - 2) products; len >= 2)

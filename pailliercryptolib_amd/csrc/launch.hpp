@@ -405,6 +405,18 @@ inline bool launch_bucket(int G, int K, const BucketArgs& a, unsigned blocks, hi
          launch_bucket_part65(G, K, a, blocks, s) || launch_bucket_part66(G, K, a, blocks, s);
 }
 
+// The encrypted 2-D convolution (hensel_conv.hpp; k_hensel.hip parts 67-69): the matmul's schedule for every output of a
+// tile of images over the window tables of launch_matvec_table, table rows addressed by arithmetic on the output position,
+// in the geometries matvec_has lists (the fold of the tap slices runs through the element-wise pair products)
+inline bool conv_has(int G, int K) { return matvec_has(G, K); }
+bool launch_conv_part67(int G, int K, const ConvArgs& a, unsigned blocks, hipStream_t s);
+bool launch_conv_part68(int G, int K, const ConvArgs& a, unsigned blocks, hipStream_t s);
+bool launch_conv_part69(int G, int K, const ConvArgs& a, unsigned blocks, hipStream_t s);
+inline bool launch_conv(int G, int K, const ConvArgs& a, unsigned blocks, hipStream_t s) {
+  return launch_conv_part67(G, K, a, blocks, s) || launch_conv_part68(G, K, a, blocks, s) ||
+         launch_conv_part69(G, K, a, blocks, s);
+}
+
 // DJN encrypt to pair rows in the same form (k_hensel.hip parts 20, 21, 28): (4,18) 2048-bit keys, (8,14) 3072, (2,19) 1024
 inline bool hensel_fb_encrypt_seq_has(int G, int K) { return (G == 4 && K == 18) || (G == 8 && K == 14) || (G == 2 && K == 19); }
 bool launch_hensel_fb_encrypt_seq_part28(int G, int K, const HenselFbArgs& a, unsigned blocks, hipStream_t s);

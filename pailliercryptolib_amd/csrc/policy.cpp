@@ -293,44 +293,39 @@ static size_t slices_rule(int G, size_t rows, size_t cols) {
   const size_t cap = std::max<size_t>(1, cols / kMatvecMinSliceCols);
   return std::max<size_t>(1, std::min(std::min(fill, cap), cols));
 }
-static size_t matmul_slices_with(long forced, int G, size_t t, size_t rows, size_t cols) {
+// a tiled call -- n items (vectors, images) of `elems` table elements each, `rows` outputs per item over `cols` terms -- for
+// both the matrix product (elems == cols) and the convolution (elems = c_in*h*w, cols = taps)
+static size_t tiled_slices_with(long forced, int G, size_t t, size_t rows, size_t cols) {
   if (forced > 0) return std::min((size_t)forced, cols);
   return slices_rule(G, t * rows, cols);
 }
-static double matmul_products_with(long forced_s, int G, size_t n_vec, size_t rows, size_t cols, int e_bits, int w, size_t tile) {
+static double tiled_products_with(long forced_s, int G, size_t n, size_t elems, size_t rows, size_t cols, int e_bits, int w, size_t tile) {
   const double nwin = (double)((e_bits + w - 1) / w);
   const auto pass = [&](size_t t) {
-    const double S = (double)matmul_slices_with(forced_s, G, t, rows, cols), out = (double)t * (double)rows;
-    return (double)t * (double)cols * (double)(((size_t)1 << w) - 2) + out * S * (double)e_bits + out * (double)cols * nwin + out * (S - 1);
+    const double S = (double)tiled_slices_with(forced_s, G, t, rows, cols), out = (double)t * (double)rows;
+    return (double)t * (double)elems * (double)(((size_t)1 << w) - 2) + out * S * (double)e_bits + out * (double)cols * nwin + out * (S - 1);
   };
-  const size_t full = n_vec / tile, rem = n_vec % tile;
+  const size_t full = n / tile, rem = n % tile;
   return (double)full * pass(tile) + (rem ? pass(rem) : 0.0);
 }
-size_t matmul_slices(int G, size_t t, size_t rows, size_t cols) {
-  if (t == 0 || rows == 0 || cols == 0) return 1;
-  return matmul_slices_with(env_now("PGPU_MATMUL_SLICES"), G, t, rows, cols);
-}
-double matmul_products(int G, size_t n_vec, size_t rows, size_t cols, int e_bits, int w, size_t tile) {
-  return matmul_products_with(env_now("PGPU_MATMUL_SLICES"), G, n_vec, rows, cols, e_bits, w, tile);
-}
-void matmul_plan(int G, size_t n_vec, size_t rows, size_t cols, int e_bits, size_t row_bytes, MatmulPlan* plan) {
-  const long fw = env_now("PGPU_MATMUL_WINDOW"), ft = env_now("PGPU_MATMUL_TILE"), fs = env_now("PGPU_MATMUL_SLICES");
+static void tiled_plan_with(long fw, long ft, long fs, int G, size_t n, size_t elems, size_t rows, size_t cols, int e_bits,
+                            size_t row_bytes, MatmulPlan* plan) {
   const int w_lo = fw > 0 ? (int)std::min(fw, 6L) : 1, w_hi = fw > 0 ? w_lo : 6;
   int best_w = w_lo;
-  size_t best_t = ft > 0 ? std::min((size_t)ft, n_vec) : 1;
+  size_t best_t = ft > 0 ? std::min((size_t)ft, n) : 1;
   double best_cost = -1;
   for (int w = w_lo; w <= w_hi; ++w) {
-    // vectors whose tables fit the cap at this window; a forced value is taken as it is
+    // items whose tables fit the cap at this window; a forced value is taken as it is
     size_t t_hi = 0;
-    if (cols <= kMatvecTableCap) t_hi = std::min(n_vec, kMatvecTableCap / (cols * ((size_t)1 << w) * row_bytes));
+    if (elems <= kMatvecTableCap) t_hi = std::min(n, kMatvecTableCap / (elems * ((size_t)1 << w) * row_bytes));
     if (t_hi == 0) {
       if (w > w_lo) break;
-      t_hi = 1;     // one oversized vector: tile = 1 at the smallest window
+      t_hi = 1;     // one oversized item: tile = 1 at the smallest window
     }
     size_t t_lo = 1;
-    if (ft > 0) t_lo = t_hi = std::min((size_t)ft, n_vec);
+    if (ft > 0) t_lo = t_hi = std::min((size_t)ft, n);
     for (size_t t = t_hi; t >= t_lo; --t) {
-      const double cost = matmul_products_with(fs, G, n_vec, rows, cols, e_bits, w, t);
+      const double cost = tiled_products_with(fs, G, n, elems, rows, cols, e_bits, w, t);
       // ties: the larger tile, then the smaller window
       if (best_cost < 0 || cost < best_cost || (cost == best_cost && (t > best_t || (t == best_t && w < best_w)))) {
         best_cost = cost;
@@ -341,11 +336,63 @@ void matmul_plan(int G, size_t n_vec, size_t rows, size_t cols, int e_bits, size
   }
   plan->window = best_w;
   plan->tile = best_t;
-  plan->passes = (n_vec + best_t - 1) / best_t;
-  plan->last = n_vec - (plan->passes - 1) * best_t;
-  plan->slices = matmul_slices_with(fs, G, best_t, rows, cols);
-  plan->last_slices = matmul_slices_with(fs, G, plan->last, rows, cols);
+  plan->passes = (n + best_t - 1) / best_t;
+  plan->last = n - (plan->passes - 1) * best_t;
+  plan->slices = tiled_slices_with(fs, G, best_t, rows, cols);
+  plan->last_slices = tiled_slices_with(fs, G, plan->last, rows, cols);
   plan->products = best_cost;
+}
+size_t matmul_slices(int G, size_t t, size_t rows, size_t cols) {
+  if (t == 0 || rows == 0 || cols == 0) return 1;
+  return tiled_slices_with(env_now("PGPU_MATMUL_SLICES"), G, t, rows, cols);
+}
+double matmul_products(int G, size_t n_vec, size_t rows, size_t cols, int e_bits, int w, size_t tile) {
+  return tiled_products_with(env_now("PGPU_MATMUL_SLICES"), G, n_vec, cols, rows, cols, e_bits, w, tile);
+}
+void matmul_plan(int G, size_t n_vec, size_t rows, size_t cols, int e_bits, size_t row_bytes, MatmulPlan* plan) {
+  tiled_plan_with(env_now("PGPU_MATMUL_WINDOW"), env_now("PGPU_MATMUL_TILE"), env_now("PGPU_MATMUL_SLICES"), G, n_vec, cols, rows,
+                  cols, e_bits, row_bytes, plan);
+}
+
+
+// ---- encrypted 2-D convolution ----
+// the matrix product's plan with the table of an item (an image's c_in*h*w elements) apart from the terms of an output
+// (its c_in*kh*kw taps)
+size_t conv_slices(int G, size_t t, size_t n_o, size_t taps) {
+  if (t == 0 || n_o == 0 || taps == 0) return 1;
+  return tiled_slices_with(env_now("PGPU_CONV_SLICES"), G, t, n_o, taps);
+}
+double conv_products(int G, size_t n_img, size_t elems, size_t n_o, size_t taps, int e_bits, int w, size_t tile) {
+  return tiled_products_with(env_now("PGPU_CONV_SLICES"), G, n_img, elems, n_o, taps, e_bits, w, tile);
+}
+void conv_plan(int G, size_t n_img, size_t elems, size_t n_o, size_t taps, int e_bits, size_t row_bytes, ConvPlan* plan) {
+  tiled_plan_with(env_now("PGPU_CONV_WINDOW"), env_now("PGPU_CONV_TILE"), env_now("PGPU_CONV_SLICES"), G, n_img, elems, n_o,
+                  taps, e_bits, row_bytes, plan);
+}
+bool conv_geometry(const size_t d[11], ConvDims* g) {
+  const size_t n_img = d[0], c_in = d[1], h = d[2], w = d[3], c_out = d[4], kh = d[5], kw = d[6], sh = d[7], sw = d[8], ph = d[9], pw = d[10];
+  constexpr size_t kSide = (size_t)1 << 30;
+  if (!n_img || !c_in || !h || !w || !c_out || !kh || !kw || !sh || !sw) return false;
+  if (ph >= kh || pw >= kw) return false;
+  if (h >= kSide || w >= kSide || kh >= kSide || kw >= kSide) return false;
+  if (kh > h + 2 * ph || kw > w + 2 * pw) return false;
+  const auto mul = [](size_t a, size_t b, size_t* r) {
+    if (a && b > ~(size_t)0 / a) return false;
+    *r = a * b;
+    return true;
+  };
+  g->oh = (h + 2 * ph - kh) / sh + 1;
+  g->ow = (w + 2 * pw - kw) / sw + 1;
+  size_t hw = h * w, kk = kh * kw, oo = g->oh * g->ow, wts, tmp;
+  if (!mul(c_in, hw, &g->elems) || !mul(n_img, g->elems, &g->x_count)) return false;
+  if (!mul(c_in, kk, &g->taps) || !mul(c_out, g->taps, &wts)) return false;
+  if (!mul(c_out, oo, &g->n_o) || !mul(n_img, g->n_o, &g->out_count)) return false;
+  // the sizes the call allocates and addresses in bytes: tables (64 entries of at most 2^11 bytes) and partial blocks
+  if (!mul(g->x_count, (size_t)1 << 17, &tmp) || !mul(g->out_count, g->taps, &tmp) || !mul(tmp, (size_t)1 << 11, &tmp)) return false;
+  // (the kernel carries channel and tap numbers in 32 bits)
+  if (c_in >= ((size_t)1 << 31) || c_out >= ((size_t)1 << 31) || g->taps >= ((size_t)1 << 31)) return false;
+  g->w_count = wts;
+  return true;
 }
 
 

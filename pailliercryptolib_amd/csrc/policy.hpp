@@ -170,6 +170,36 @@ double matmul_products(int G, size_t n_vec, size_t rows, size_t cols, int e_bits
 void matmul_plan(int G, size_t n_vec, size_t rows, size_t cols, int e_bits, size_t row_bytes, MatmulPlan* plan);
 
 
+// ---- the encrypted 2-D convolution (hensel_conv.hpp; pgpu_batch_ct_conv2d, pgpu_ct_conv2d_plan) ----
+// out[n][co][oy][ox] = prod_{ci,ky,kx} x[n][ci][oy*sh + ky - ph][ox*sw + kx - pw]^w[co][ci][ky][kx] for n_img images: the
+// matrix product above with the table of an item apart from the terms of an output.  The tile is whole images per pass.
+// With elems = c_in*h*w (the table elements of an image), n_o = c_out*oh*ow (its outputs) and taps = c_in*kh*kw (the terms
+// of an output, padded ones counted: they are multiplied by one), a pass over t images costs, in pair products,
+//     t * elems * (2^w - 2)               table build
+//   + t * n_o * S * e_bits                squarings
+//   + t * n_o * taps * ceil(e_bits / w)   multiplications by table entries
+//   + t * n_o * (S - 1)                   fold of the partial products,
+// with S the matvec's slice rule for t * n_o outputs over taps columns -- carried over as it stands, not fitted to this
+// kernel (the short last pass of a call has its own S).
+// conv_plan: w in 1..6 and tile in 1..n_img with tile * elems * 2^w * row_bytes <= kMatvecTableCap, the pair with the
+// fewest products of the whole call; ties go to the larger tile, then to the smaller window.  Where one image's table at
+// w = 1 exceeds the cap: tile = 1, w = 1.  A kernel equal to the image without padding and n_img = 1 gives matvec_window
+// and matvec_slices for rows = c_out, cols = elems.
+// PGPU_CONV_WINDOW=w, PGPU_CONV_TILE=t, PGPU_CONV_SLICES=S force the three values (clamped to 1..6, 1..n_img, 1..taps; a
+// forced S holds for every pass; a forced value is not held against the cap; read at every call).
+using ConvPlan = MatmulPlan;   // tile / last: images of a pass
+size_t conv_slices(int G, size_t t, size_t n_o, size_t taps);
+double conv_products(int G, size_t n_img, size_t elems, size_t n_o, size_t taps, int e_bits, int w, size_t tile);
+void conv_plan(int G, size_t n_img, size_t elems, size_t n_o, size_t taps, int e_bits, size_t row_bytes, ConvPlan* plan);
+// the sizes of a shape d = {n_img, c_in, h, w, c_out, kh, kw, stride_h, stride_w, pad_h, pad_w} (the order of
+// pgpu_conv2d_shape).  false -- what both C-ABI calls refuse of a shape alone: a dimension or stride equal to 0, pad >=
+// kernel, kernel > padded image, an image or kernel side of 2^30 or more, a size product beyond size_t.
+struct ConvDims {
+  size_t oh, ow, elems, taps, n_o, x_count, w_count, out_count;
+};
+bool conv_geometry(const size_t d[11], ConvDims* g);
+
+
 // ---- the encrypted segmented sum (hensel_segsum.hpp; pgpu_batch_ct_segment_sum, pgpu_ct_segment_sum_plan) ----
 // out[g][s] = prod_{j : ids[g][j] == s} X[j].  A segment of m elements costs m - 1 pair products however it is cut, so the
 // cut decides only how the products spread over the chip and what each chain pays beside them.

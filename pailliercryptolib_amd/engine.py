@@ -235,6 +235,52 @@ class PublicKey:
         inner = n_vec if transposed else len(rows)
         return [out[k:k + inner] for k in range(0, len(out), inner)]
 
+    def conv2d(self, x, w, stride=1, padding=0, e_bits=None):
+        """Encrypted 2-D convolution: x nested lists [n_img][C_in][H][W] of ciphertexts (ints modulo n^2), w nested lists
+        [C_out][C_in][kh][kw] of non-negative ints, stride and padding an int or a (vertical, horizontal) pair -> nested
+        lists [n_img][C_out][OH][OW] of ciphertexts, OH = (H + 2 pad_h - kh) // stride_h + 1, OW likewise,
+        out[n][co][oy][ox] = prod_{ci,ky,kx} x[n][ci][oy*stride_h + ky - pad_h][ox*stride_w + kx - pad_w]^w[co][ci][ky][kx]
+        mod n^2 with taps outside the image left out (zero padding), i.e. encryptions of what
+        torch.nn.functional.conv2d(m, w, stride=stride, padding=padding) computes, mod n.  One pgpu_batch_ct_conv2d call on
+        resident batches (window tables per tile of images, addressed by the output position: no index list); there is
+        no element-wise fall-back and none through ``spmv``."""
+        def pair(v, what):
+            p = (v, v) if isinstance(v, int) else tuple(v)
+            if len(p) != 2 or any(int(q) != q or q < 0 for q in p):
+                raise RuntimeError(f"conv2d error: {what} must be a non-negative int or a pair of them")
+            return int(p[0]), int(p[1])
+        (sh, sw), (ph, pw) = pair(stride, "stride"), pair(padding, "padding")
+        try:
+            xs = [[[list(row) for row in ch] for ch in img] for img in x]
+            ws = [[[list(row) for row in ch] for ch in f] for f in w]
+            n_img, c_in, h, wd = len(xs), len(xs[0]), len(xs[0][0]), len(xs[0][0][0])
+            c_out, kh, kw = len(ws), len(ws[0][0]), len(ws[0][0][0])
+        except (TypeError, IndexError):
+            raise RuntimeError("conv2d error: Size mismatch! (x must be [n_img][C_in][H][W], w [C_out][C_in][kh][kw])") from None
+        if not (n_img and c_in and h and wd and c_out and kh and kw) or \
+                any(len(img) != c_in or any(len(ch) != h or any(len(row) != wd for row in ch) for ch in img) for img in xs) or \
+                any(len(f) != c_in or any(len(ch) != kh or any(len(row) != kw for row in ch) for ch in f) for f in ws):
+            raise RuntimeError("conv2d error: Size mismatch! (x must be [n_img][C_in][H][W], w [C_out][C_in][kh][kw])")
+        if sh < 1 or sw < 1:
+            raise RuntimeError("conv2d error: the stride must be positive")
+        if ph >= kh or pw >= kw:
+            raise RuntimeError("conv2d error: the padding must be smaller than the kernel")
+        if kh > h + 2 * ph or kw > wd + 2 * pw:
+            raise RuntimeError("conv2d error: the kernel exceeds the padded image")
+        flat = [int(v) for f in ws for ch in f for row in ch for v in row]
+        if min(flat) < 0:
+            raise RuntimeError("conv2d error: negative weights have no encoding (pass w mod n)")
+        if e_bits is None:
+            e_bits = max(1, max(v.bit_length() for v in flat))
+        ew = (int(e_bits) + 63) // 64
+        oh, ow = (h + 2 * ph - kh) // sh + 1, (wd + 2 * pw - kw) // sw + 1
+        shape = _capi.Conv2dShape(n_img, c_in, h, wd, c_out, kh, kw, sh, sw, ph, pw)
+        cts = [c for img in xs for ch in img for row in ch for c in row]
+        out = self._resident_call([self._ct(cts), (flat, ew)], n_img * c_out * oh * ow, lambda L, hd, o:
+                                  L.pgpu_batch_ct_conv2d(self._h, hd[0], hd[1], ctypes.byref(shape), int(e_bits), o))
+        it = iter(out)
+        return [[[[next(it) for _ in range(ow)] for _ in range(oh)] for _ in range(c_out)] for _ in range(n_img)]
+
     def spmv(self, x, indptr, indices, w, e_bits=None):
         """Encrypted sparse matrix-vector product: x a list of ciphertexts (ints modulo n^2), the plaintext matrix in CSR
         form -- indptr (rows + 1 offsets, starting at 0), indices (a column of x per entry), w (a non-negative int per
