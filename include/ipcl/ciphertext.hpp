@@ -26,6 +26,9 @@ CipherText conv2d(const PlainText& w, const CipherText& x, const Conv2dShape& sh
 CipherText segmentSum(const CipherText& x, const std::vector<uint32_t>& ids, std::size_t n_segments, std::size_t groups);
 CipherText segmentScan(const CipherText& x, std::size_t seg_len, bool reverse);
 CipherText packSlots(const CipherText& x, std::size_t seg_len, std::size_t slot_bits);
+// include/ipcl/ext/arith.hpp
+CipherText negate(const CipherText& x);
+CipherText subtract(const CipherText& a, const CipherText& b);
 }
 
 class CipherText : public BaseText {
@@ -81,6 +84,10 @@ class CipherText : public BaseText {
   friend CipherText ext::packSlots(const CipherText& x, std::size_t seg_len, std::size_t slot_bits);
   // prod_t this[r][t]^(2^(slot_bits t)), this read as [m_size / seg_len][seg_len]: csrc/host/aggregate.cpp
   CipherText packMap(std::size_t seg_len, std::size_t slot_bits) const;
+  friend CipherText ext::negate(const CipherText& x);
+  friend CipherText ext::subtract(const CipherText& a, const CipherText& b);
+  // this[i] * b[i]^-1 mod n^2 (b == null: this[i]^-1), all inverses from one modular inversion: csrc/host/arith.cpp
+  CipherText inverseMap(const CipherText* b) const;
   CipherText(const PublicKey& pk, std::shared_ptr<detail::DeviceBatch> dev);
   CipherText(std::shared_ptr<PublicKey> pk, std::shared_ptr<detail::DeviceBatch> dev);
   std::shared_ptr<PublicKey> m_pk;

@@ -9,7 +9,8 @@
 //   segmentScan(x, seg_len, reverse = false)
 //       x read as [x.getSize() / seg_len][seg_len]; y[r][t] = sum of x[r][u], u <= t (reverse: u >= t) under the encryption:
 //       Y[r][t] = prod_{u <= t} X[r][u] mod n^2 -- the cumulative sum over the bins of every histogram that segmentSum made
-//       (seg_len = n_segments), both sides of every split without a subtraction; a running total over one long vector
+//       (seg_len = n_segments), both sides of every split from two scans (cheaper than ipcl/ext/arith.hpp's subtract of the
+//       left side from the total); a running total over one long vector
 //       with seg_len = x.getSize().  The scan is inclusive.  seg_len must be positive and divide x.getSize().
 //
 //   packSlots(x, seg_len, slot_bits)

@@ -71,7 +71,7 @@ typedef enum pgpu_status {
   PGPU_ERR_UNSUPPORTED = -3,   /* operand width beyond the compiled kernel geometries      */
   PGPU_ERR_NO_DEVICE = -4,     /* no HIP device / not initialised                          */
   PGPU_ERR_HIP = -5,           /* a HIP runtime call failed (see pgpu_last_error)          */
-  PGPU_ERR_NOT_INVERTIBLE = -6 /* key material is inconsistent (e.g. p == q)               */
+  PGPU_ERR_NOT_INVERTIBLE = -6 /* key material is inconsistent (e.g. p == q); negate / sub of a non-unit */
 } pgpu_status;
 
 /* ---- context: behind ipcl::initializeContext / terminateContext (utils/context.cpp:40-71);
@@ -577,6 +577,42 @@ int pgpu_batch_ct_conv2d(const pgpu_pubkey* key, const pgpu_batch* x, const pgpu
 int pgpu_ct_conv2d_plan(int key_bits, const pgpu_conv2d_shape* shape, int e_bits, int* window, int* slices, size_t* tile,
                         size_t* table_bytes, size_t* products);
 
+/* Ciphertext negation and subtraction: x (a, b) resident ciphertext batches of count elements under key (pair rows, or
+ * uploaded plain ciphertext words: converted on the way in):
+ *     negate   out[i] = x[i]^-1 mod n^2              i.e. Dec(out[i]) = -Dec(x[i]) mod n
+ *     sub      out[i] = a[i] * b[i]^-1 mod n^2       i.e. Dec(out[i]) = Dec(a[i]) - Dec(b[i]) mod n
+ * b has count(a) elements, or one (the broadcast pgpu_batch_ct_add allows: one inverse, multiplied into every a[i]).  The
+ * result is an ordinary resident ciphertext batch of count elements in pair rows on the lane of the first operand
+ * (operands of other lanes are ordered in by events, as for pgpu_batch_ct_add); the operands are left unchanged.  The
+ * downloaded result is the canonical value: pow(c, -1, n^2), and a * pow(b, -1, n^2) mod n^2.
+ * All inverses of a batch come from ONE modular inversion by simultaneous inversion ("Ciphertext negation and
+ * subtraction"): a forward pass stores the running products of chains of `chunk` rows, the chain totals are inverted by the
+ * same procedure, and every chain is walked back from the inverse of its total -- 3 * (count - 1) pair products for
+ * negate, count more for sub (multiplied in by the last walk: no extra launch, no intermediate batch), where
+ * pgpu_batch_ct_mul by n - 1 runs about 2400 per element of a 2048-bit key.  The one inversion is the HOST's: per call one
+ * row travels down, the lane's stream is synchronised once, one row travels up.  That inversion is variable-time over a
+ * product of ciphertexts, which is public data.
+ * PGPU_ERR_INVALID_PARAM: null / stale handles, a null out, count(b) neither count(a) nor 1, ciphertext width mismatch, a
+ * batch of another key, more chains than the descriptors address.
+ * PGPU_ERR_UNSUPPORTED: keys without pair rows (beyond 3072 bits; PGPU_PAIR_ROWS=0 / PGPU_HENSEL=0), pools of more than one
+ * GPU, and the masked table-gather policy.  SIDE CHANNELS: the address stream of these calls depends only on count and the
+ * plan; the refusal under pgpu_set_table_gather_policy(1) is kept so that one rule covers the aggregation calls.
+ * These refusals are decided on the host before any launch and leave *out untouched.
+ * PGPU_ERR_NOT_INVERTIBLE: the product of the batch (for sub: of b) is not a unit modulo n -- an element is 0 or shares a
+ * factor with n; neither is a ciphertext.  This ONE refusal FOLLOWS LAUNCHES: it is known when the host has the grand
+ * total, after the forward passes.  It leaves *out untouched, frees what the call allocated, and the lane stays usable. */
+int pgpu_batch_ct_negate(const pgpu_pubkey* key, const pgpu_batch* x, pgpu_batch** out);
+int pgpu_batch_ct_sub(const pgpu_pubkey* key, const pgpu_batch* a, const pgpu_batch* b, pgpu_batch** out);
+/* What a negate of this size would run (host-side query, needs no device; every output pointer may be NULL).  chunk: the
+ * rows of one chain of the first level (the levels above it, which cannot fill the chip, are cut into pairs); levels: the
+ * depth of the hierarchy, 1 when count <= chunk; launches: what the timing record shows as
+ * PGPU_KERNEL_INVERT for pair-row input, a forward pass and a walk back per level -- count == 1 has nothing to multiply
+ * forward and is one walk back; products: 3 * (count - 1), padding excluded.  The rule is policy.hpp: invert_*;
+ * PGPU_INVERT_CHUNK=c (c >= 2) forces the chunk of every level, PGPU_INVERT_WIDE=0 / 1 its form, read at every call.
+ * PGPU_ERR_UNSUPPORTED: no pair rows for keys of key_bits.  PGPU_ERR_INVALID_PARAM: key_bits < 1, count == 0, more chains
+ * than the descriptors address. */
+int pgpu_ct_negate_plan(int key_bits, size_t count, int* chunk, int* levels, int* launches, size_t* products);
+
 /* ---- instrumentation used by bench.py (roofline) ----
  * With timing enabled every kernel launch is bracketed by two HIP events recorded on the stream
  * the kernel is launched on (no synchronisation at launch time).  pgpu_timing_collect waits for
@@ -595,7 +631,8 @@ typedef enum pgpu_kernel_kind {
   PGPU_KERNEL_WSUM = 10,      /* every launch of pgpu_batch_ct_weighted_sum: the slices' schedules, the fold */
   PGPU_KERNEL_MATMUL = 11,    /* every launch of pgpu_batch_ct_matmul: per pass the table build, the multi-exponentiation, the fold */
   PGPU_KERNEL_BUCKET = 12,    /* every launch of pgpu_batch_ct_matvec_bucket: accumulation levels, bucket reductions, Horner */
-  PGPU_KERNEL_CONV = 13       /* every launch of pgpu_batch_ct_conv2d: per pass the table build, the multi-exponentiation, the fold */
+  PGPU_KERNEL_CONV = 13,      /* every launch of pgpu_batch_ct_conv2d: per pass the table build, the multi-exponentiation, the fold */
+  PGPU_KERNEL_INVERT = 14     /* every launch of pgpu_batch_ct_negate / _sub: forward passes, walks back, the broadcast product */
 } pgpu_kernel_kind;
 int pgpu_set_timing(int enabled);
 int pgpu_timing_collect(int* kinds, double* ms, int max_entries);

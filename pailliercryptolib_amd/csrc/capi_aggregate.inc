@@ -1,5 +1,5 @@
 // pailliercryptolib_amd -- the aggregation calls on resident ciphertexts (pgpu_batch_ct_matvec / _matvec_bucket / _matmul / _conv2d / _spmv / _weighted_sum /
-// _segment_sum / _segment_scan / _pack) and their plan queries (pgpu_ct_*_plan).
+// _segment_sum / _segment_scan / _pack / _negate / _sub) and their plan queries (pgpu_ct_*_plan).
 // Part of the translation unit of capi.cpp (included there, in place, after capi_batches.inc, whose bounce buffer the plan
 // upload shares).  Every call is: its own parameter checks, the admission tail, its plan (policy.hpp), the result set-up,
 // one upload of the plan image, its launches.  What the calls have in common is written once, in the helpers below.
@@ -970,5 +970,187 @@ int pgpu_batch_ct_pack(const pgpu_pubkey* key, const pgpu_batch* x, size_t seg_l
   a.slot_bits = (uint32_t)slot_bits;
   a.out = r.o->prow(0);
   RC_TRY(timed_launch(r, rows, lf->H, PGPU_KERNEL_PACK, "pack", [&](unsigned blocks) { return pgpu::launch_pack(lf->H, lf->K, a, blocks, r.s); }));
+  return r.finish(out);
+}
+
+// ---- ciphertext negation and subtraction (hensel_invert.hpp; policy.hpp: invert_*) ----
+int pgpu_ct_negate_plan(int key_bits, size_t count, int* chunk, int* levels, int* launches, size_t* products) {
+  if (key_bits < 1 || count == 0) return fail(PGPU_ERR_INVALID_PARAM, "negate plan: key_bits and count must be positive");
+  int G = 0, K = 0;
+  if (!policy::matvec_geometry(key_bits, &G, &K))
+    return fail(PGPU_ERR_UNSUPPORTED, "negate: keys of this size have no pair rows (1024- to 3072-bit key classes only)");
+  if (!policy::invert_fits(G, count))
+    return fail(PGPU_ERR_INVALID_PARAM, "negate plan: more chains than a 32-bit descriptor field addresses");
+  if (chunk) *chunk = policy::invert_chunk(G, count);
+  if (levels) *levels = policy::invert_levels(G, count);
+  if (launches) *launches = policy::invert_launches(G, count);
+  if (products) *products = policy::invert_products(count);
+  return PGPU_OK;
+}
+
+namespace {
+// res[i] = x[i]^-1 mod n^2 (mul != null: mul[i] * x[i]^-1) as a new pair batch of count(x) rows on `lane`; the callers have
+// made every check but the plan's.  The one refusal after launches: PGPU_ERR_NOT_INVERTIBLE (nothing is handed out then;
+// what was allocated goes back to the lane's arena behind the launches, as after any call)
+int invert_batch(const pgpu_pubkey* key, const pgpu_pubkey::PubForm* pf, const char* name, const pgpu_batch* x0,
+                 const pgpu_batch* mul0, int lane, std::unique_ptr<pgpu_batch>* res) {
+  const size_t count = x0->count;
+  const int W = 2 * key->n_words;
+  const size_t LQ = (size_t)2 * pf->H * pf->K, row_bytes = LQ * sizeof(uint32_t);
+  // the plan, on the host
+  if (!policy::invert_fits(pf->H, count))
+    return fail(PGPU_ERR_INVALID_PARAM, std::string(name) + " error: more chains than a 32-bit descriptor field addresses (a larger PGPU_INVERT_CHUNK, or fewer elements per call)");
+  policy::InvertPlan plan;
+  policy::InvertImage img;
+  try {
+    policy::invert_plan(count, pf->H, &plan);
+    policy::invert_image(plan, &img);
+  } catch (const std::bad_alloc&) {
+    return fail(PGPU_ERR_INVALID_PARAM, std::string(name) + " error: the plan does not fit host memory (fewer elements per call)");
+  }
+  const size_t nl = plan.levels.size();
+  // the operands as pair rows, each converted on its own lane
+  std::unique_ptr<pgpu_batch> tx, tm;
+  const pgpu_batch *x = nullptr, *mul = nullptr;
+  RC_TRY(as_pair_batch(key, x0, &x, &tx));
+  if (mul0) RC_TRY(as_pair_batch(key, mul0, &mul, &tm));
+  AggRun r;
+  RC_TRY(r.open_out(key, pf, count, lane));
+  RC_TRY(lanes_order(x, lane, true));
+  RC_TRY(lanes_order(mul, lane, true));
+  Bounce& bn = bounce();
+  RC_TRY(bn.ready());
+  // scratch: the levels above the first; io: the inverse of the grand total as a pair row, then the total and its inverse as words
+  rt::DevMem dimage, scratch, io;
+  if (img.scratch_rows) RC_TRY(scratch.alloc(*r.dev, r.s, img.scratch_rows * row_bytes));
+  RC_TRY(io.alloc(*r.dev, r.s, row_bytes + 2 * (size_t)W * sizeof(uint64_t)));
+  RC_TRY(upload_plan_image(*r.dev, r.s, img.image.data(), img.image.size(), &dimage));
+  const pgpu_pubkey::PubForm* wide = wide_form(key, pf, pgpu::invert_wide_has);
+  auto form_of = [&](size_t chains) { return wide && policy::invert_wide_pays(wide->H, chains) ? wide : pf; };
+  uint32_t* const sc = (uint32_t*)scratch.p;
+  // level l reads in(l) and writes res(l) -- first its running products, then, over them, its inverses
+  auto in = [&](size_t l) -> const uint32_t* { return l == 0 ? x->prow(0) : sc + img.in_at[l] * LQ; };
+  auto at = [&](size_t l) -> uint32_t* { return l == 0 ? r.o->prow(0) : sc + img.out_at[l] * LQ; };
+  for (size_t l = 0; l < nl; ++l) {       // forward: the running products of every chain, level by level
+    const auto& lv = plan.levels[l];
+    if (l) {
+      // the totals of the level below -- the last running product of each of its chains -- side by side: the chains of full
+      // length end chunk rows apart, the last one ends with the level
+      const size_t below = plan.levels[l - 1].n, c = (size_t)plan.levels[l - 1].chunk, full = below / c;
+      uint32_t* dst = sc + img.in_at[l] * LQ;
+      if (full)
+        HIP_TRY(hipMemcpy2DAsync(dst, row_bytes, at(l - 1) + (c - 1) * LQ, c * row_bytes, row_bytes, full, hipMemcpyDeviceToDevice, r.s));
+      if (full < lv.n)
+        HIP_TRY(hipMemcpyAsync(dst + full * LQ, at(l - 1) + (below - 1) * LQ, row_bytes, hipMemcpyDeviceToDevice, r.s));
+    }
+    if (lv.n == 1) break;                 // (count == 1: a chain of one entry has nothing to multiply)
+    const pgpu_pubkey::PubForm* lf = form_of(lv.fwd.size());
+    pgpu::SegscanArgs a{};
+    a.ctx = hensel_pub_view(lf, r.dev->index);
+    a.src = in(l);
+    a.chunks = (const pgpu::SegscanChunk*)((const char*)dimage.p + img.fwd_at[l]);
+    a.n_chunks = lv.fwd.size();
+    a.out = at(l);
+    a.step = 1;
+    RC_TRY(timed_launch(r, a.n_chunks, lf->H, PGPU_KERNEL_INVERT, name, [&](unsigned blocks) { return pgpu::launch_segscan(lf->H, lf->K, a, blocks, r.s); }));
+  }
+  {
+    // the one inversion, on the host: the grand total travels down as the plain value, its inverse up
+    const size_t top = plan.levels[nl - 1].n;
+    const uint32_t* total = top == 1 ? in(nl - 1) : at(nl - 1) + (top - 1) * LQ;
+    uint64_t* const dw = (uint64_t*)((char*)io.p + row_bytes);
+    RC_TRY(pair_to_words_on(*r.dev, pf, total, dw, 1, r.s, (size_t)W));
+    HIP_TRY(rt::drain_before_copy(r.s));
+    HIP_TRY(hipMemcpyAsync(bn.p, dw, (size_t)W * sizeof(uint64_t), hipMemcpyDeviceToHost, r.s));   // (behind the plan upload that read bn.p)
+    HIP_TRY(hipStreamSynchronize(r.s));
+    bn.pending = false;
+    std::vector<uint64_t> inv_words((size_t)W, 0);
+    try {
+      const BigNumber nsq = key->n * key->n;
+      const BigNumber inv = nsq.InverseMul(BigNumber::fromLimbs64((const uint64_t*)bn.p, (size_t)W));
+      inv.toLimbs64(inv_words.data(), inv_words.size());
+    } catch (const std::runtime_error&) {
+      RC_TRY(lanes_order(x, lane, false));
+      RC_TRY(lanes_order(mul, lane, false));
+      return fail(PGPU_ERR_NOT_INVERTIBLE, std::string(name) + " error: the product of the batch is not a unit modulo n (an element is 0 or shares a factor with n: not a ciphertext)");
+    }
+    std::memcpy(bn.p, inv_words.data(), (size_t)W * sizeof(uint64_t));
+    HIP_TRY(hipMemcpyAsync(dw + W, bn.p, (size_t)W * sizeof(uint64_t), hipMemcpyHostToDevice, r.s));
+    HIP_TRY(hipEventRecord(bn.ev, r.s));
+    bn.pending = true;
+    RC_TRY(words_to_pair_on(*r.dev, pf, dw + W, (size_t)W, W, false, (uint32_t*)io.p, 1, r.s));
+  }
+  for (size_t l = nl; l-- > 0;) {         // walk back: the top level from the uploaded inverse, every other one from the level above
+    const auto& lv = plan.levels[l];
+    const pgpu_pubkey::PubForm* lf = form_of(lv.back.size());
+    pgpu::InvertArgs a{};
+    a.ctx = hensel_pub_view(lf, r.dev->index);
+    a.x = in(l);
+    a.p = at(l);
+    a.u = l + 1 < nl ? at(l + 1) : (const uint32_t*)io.p;
+    a.mul = l == 0 && mul ? mul->prow(0) : nullptr;
+    a.chunks = (const pgpu::SegscanChunk*)((const char*)dimage.p + img.back_at[l]);
+    a.n_chunks = lv.back.size();
+    a.out = at(l);
+    RC_TRY(timed_launch(r, a.n_chunks, lf->H, PGPU_KERNEL_INVERT, name, [&](unsigned blocks) { return pgpu::launch_invert(lf->H, lf->K, a, blocks, r.s); }));
+  }
+  RC_TRY(lanes_order(x, lane, false));
+  RC_TRY(lanes_order(mul, lane, false));
+  *res = std::move(r.o);
+  return PGPU_OK;
+}
+}  // namespace
+
+int pgpu_batch_ct_negate(const pgpu_pubkey* key, const pgpu_batch* x, pgpu_batch** out) {
+  RC_TRY(rt::check_ready());
+  if (!key || !x || !out) return fail(PGPU_ERR_INVALID_PARAM, "null argument");
+  RC_TRY(check_gen(key->gen, "key"));
+  RC_TRY(check_gen(x->gen, "batch"));
+  if (x->words != 2 * key->n_words) return fail(PGPU_ERR_INVALID_PARAM, "negate error: ciphertext width mismatch");
+  // (the address stream here depends on count and the plan alone)
+  static const AggOp op{"negate", "elements", kNoMaskedVariant, pgpu::invert_has, nullptr};
+  const pgpu_pubkey::PubForm* pf = nullptr;
+  RC_TRY(agg_admit(op, key, &x, 1, &pf));
+  std::unique_ptr<pgpu_batch> o;
+  RC_TRY(invert_batch(key, pf, "negate", x, nullptr, x->lane, &o));
+  *out = o.release();
+  return PGPU_OK;
+}
+
+int pgpu_batch_ct_sub(const pgpu_pubkey* key, const pgpu_batch* a, const pgpu_batch* b, pgpu_batch** out) {
+  RC_TRY(rt::check_ready());
+  if (!key || !a || !b || !out) return fail(PGPU_ERR_INVALID_PARAM, "null argument");
+  RC_TRY(check_gen(key->gen, "key"));
+  RC_TRY(check_gen(a->gen, "batch"));
+  RC_TRY(check_gen(b->gen, "batch"));
+  const int W = 2 * key->n_words;
+  if (a->words != W || b->words != W) return fail(PGPU_ERR_INVALID_PARAM, "CT - CT error: ciphertext width mismatch");
+  if (b->count != a->count && b->count != 1) return fail(PGPU_ERR_INVALID_PARAM, "CT - CT error: Size mismatch! (b must hold count(a) elements, or one)");
+  static const AggOp op{"CT - CT", "elements", kNoMaskedVariant, pgpu::invert_has, nullptr};
+  const pgpu_pubkey::PubForm* pf = nullptr;
+  const pgpu_batch* const both[2] = {a, b};
+  RC_TRY(agg_admit(op, key, both, 2, &pf));
+  std::unique_ptr<pgpu_batch> o;
+  if (b->count == a->count) {             // the last walk multiplies a[i] in: no extra launch, no intermediate batch
+    RC_TRY(invert_batch(key, pf, "CT - CT", b, a, a->lane, &o));
+    *out = o.release();
+    return PGPU_OK;
+  }
+  // broadcast: ONE inverse, multiplied into every a[i] (the element-wise pair product of CT + CT, one shared row)
+  std::unique_ptr<pgpu_batch> binv, ta;
+  RC_TRY(invert_batch(key, pf, "CT - CT", b, nullptr, a->lane, &binv));
+  RC_TRY(as_pair_batch(key, a, &a, &ta));
+  AggRun r;
+  RC_TRY(r.open_out(key, pf, a->count, a->lane));
+  pgpu::PairOpsArgs pa{};
+  const pgpu_pubkey::PubForm* lf = pair_op_form(key, pf, a->count);
+  pa.ctx = hensel_pub_view(lf, r.dev->index);
+  pa.op = pgpu::PO_MUL;
+  pa.a = a->prow(0);
+  pa.b = binv->prow(0);
+  pa.b_stride = 0;
+  pa.out = r.o->prow(0);
+  pa.count = a->count;
+  RC_TRY(pair_op_launch(*r.dev, lf, pa, r.s, PGPU_KERNEL_INVERT));
   return r.finish(out);
 }

@@ -1,5 +1,5 @@
 // pailliercryptolib_amd -- instantiations of the split-form CRT-decrypt exponentiation (hensel.hpp), split over
-// PGPU_PART = 0..69 so that they compile in parallel (67-69: the encrypted 2-D convolution; 63-66: the bucket reduction of the bucket-method matvec; 60-62: the encrypted matrix product; 56-59: the encrypted weighted sum of K resident batches; 53-55: the encrypted sparse matrix-vector product; 38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 45-47: the encrypted segmented prefix sum; 48-51: the encrypted slot packing; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
+// PGPU_PART = 0..74 so that they compile in parallel (70-73: the walk back of the batched inversion, 74: its forward pass in the (8,9) form; 67-69: the encrypted 2-D convolution; 63-66: the bucket reduction of the bucket-method matvec; 60-62: the encrypted matrix product; 56-59: the encrypted weighted sum of K resident batches; 53-55: the encrypted sparse matrix-vector product; 38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 45-47: the encrypted segmented prefix sum; 48-51: the encrypted slot packing; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
 // the two-wavefronts-per-SIMD build of the (2,19) decrypt form; 11-13: element-wise operations on pair rows).
 #include "hensel_seq.hpp"
 #include "launch.hpp"
@@ -21,7 +21,7 @@
 #if defined(PGPU_PART) && PGPU_PART >= 41 && PGPU_PART <= 44
 #include "hensel_segsum.hpp"    // the encrypted segmented sum: one product chain per chunk of a sorted index list
 #endif
-#if defined(PGPU_PART) && PGPU_PART >= 45 && PGPU_PART <= 47
+#if defined(PGPU_PART) && ((PGPU_PART >= 45 && PGPU_PART <= 47) || PGPU_PART == 74)
 #include "hensel_segscan.hpp"   // the encrypted segmented prefix sum: one product chain per chunk, every step stored
 #endif
 #if defined(PGPU_PART) && PGPU_PART >= 48 && PGPU_PART <= 51
@@ -42,9 +42,12 @@
 #if defined(PGPU_PART) && PGPU_PART >= 67 && PGPU_PART <= 69
 #include "hensel_conv.hpp"      // the encrypted 2-D convolution: the matmul's schedule, table rows by arithmetic on the output position
 #endif
+#if defined(PGPU_PART) && PGPU_PART >= 70 && PGPU_PART <= 73
+#include "hensel_invert.hpp"    // the batched inversion (negate / subtract): the walk back over the chains of the forward pass
+#endif
 
 #ifndef PGPU_PART
-#error "compile with -DPGPU_PART=0..69 (15 and 30 are retired)"
+#error "compile with -DPGPU_PART=0..74 (15 and 30 are retired)"
 #endif
 
 namespace pgpu {
@@ -526,8 +529,8 @@ bool PGPU_SS_NAME(int G, int K, const SegsumArgs& a, unsigned blocks, hipStream_
   hipLaunchKernelGGL((segsum_kernel<PGPU_SS_G, PGPU_SS_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
   return true;
 }
-#elif PGPU_PART >= 45 && PGPU_PART <= 47
-// the encrypted segmented prefix sum (hensel_segscan.hpp): one geometry per part
+#elif (PGPU_PART >= 45 && PGPU_PART <= 47) || PGPU_PART == 74
+// the encrypted segmented prefix sum (hensel_segscan.hpp): one geometry per part; 74 is the 2048-bit class on 8 lanes
 #if PGPU_PART == 45
 #define PGPU_SC_G 4
 #define PGPU_SC_K 18
@@ -536,10 +539,14 @@ bool PGPU_SS_NAME(int G, int K, const SegsumArgs& a, unsigned blocks, hipStream_
 #define PGPU_SC_G 8
 #define PGPU_SC_K 14
 #define PGPU_SC_NAME launch_segscan_part46
-#else
+#elif PGPU_PART == 47
 #define PGPU_SC_G 2
 #define PGPU_SC_K 19
 #define PGPU_SC_NAME launch_segscan_part47
+#else
+#define PGPU_SC_G 8
+#define PGPU_SC_K 9
+#define PGPU_SC_NAME launch_segscan_part74
 #endif
 bool PGPU_SC_NAME(int G, int K, const SegscanArgs& a, unsigned blocks, hipStream_t s) {
   if (G != PGPU_SC_G || K != PGPU_SC_K) return false;
@@ -676,6 +683,31 @@ bool PGPU_BK_NAME(int G, int K, const BucketArgs& a, unsigned blocks, hipStream_
 bool PGPU_CV_NAME(int G, int K, const ConvArgs& a, unsigned blocks, hipStream_t s) {
   if (G != PGPU_CV_G || K != PGPU_CV_K) return false;
   hipLaunchKernelGGL((conv_kernel<PGPU_CV_G, PGPU_CV_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
+  return true;
+}
+#elif PGPU_PART >= 70 && PGPU_PART <= 73
+// the walk back of the batched inversion (hensel_invert.hpp): one geometry per part; 73 is the 2048-bit class on 8 lanes
+#if PGPU_PART == 70
+#define PGPU_IV_G 2
+#define PGPU_IV_K 19
+#define PGPU_IV_NAME launch_invert_part70
+#elif PGPU_PART == 71
+#define PGPU_IV_G 4
+#define PGPU_IV_K 18
+#define PGPU_IV_NAME launch_invert_part71
+#elif PGPU_PART == 72
+#define PGPU_IV_G 8
+#define PGPU_IV_K 14
+#define PGPU_IV_NAME launch_invert_part72
+#else
+#define PGPU_IV_G 8
+#define PGPU_IV_K 9
+#define PGPU_IV_NAME launch_invert_part73
+#endif
+bool PGPU_IV_NAME(int G, int K, const InvertArgs& a, unsigned blocks, hipStream_t s) {
+  if (G != PGPU_IV_G || K != PGPU_IV_K) return false;
+  if (a.mul) hipLaunchKernelGGL((invert_walk_kernel<PGPU_IV_G, PGPU_IV_K, true>), dim3(blocks), dim3(kWGThreads), 0, s, a);
+  else hipLaunchKernelGGL((invert_walk_kernel<PGPU_IV_G, PGPU_IV_K, false>), dim3(blocks), dim3(kWGThreads), 0, s, a);
   return true;
 }
 #else

@@ -373,6 +373,25 @@ struct SegscanArgs {
   int step;                  // +1: prefix products, -1: suffix products
 };
 
+// Walk back of the batched inversion on pair rows (hensel_invert.hpp; pgpu_batch_ct_negate / _sub): one chain per chunk
+// descriptor -- the descriptors of the forward pass (a one-level segscan_kernel launch over the same chains, which left the
+// running products P[begin + t] = x[begin] * ... * x[begin + t] in `p`), with `carry` naming the row of `u` that holds the
+// inverse of the chain's total P[begin + len - 1].  From U = that row, for t = len - 1 down to 1,
+//     out[begin + t] = P[begin + t - 1] * U,   U = U * x[begin + t],      and out[begin] = U:
+// out[i] = x[i]^-1 for every row, two products per entry and none for the first.  mul != null: every result is multiplied
+// by mul[begin + t] before it is stored (the subtraction's a[i] * b[i]^-1, one product more per entry).  p may be the
+// same memory as out: a chain reads row t - 1 before it stores row t, and no other chain touches its rows.
+struct InvertArgs {
+  HenselPubDev ctx;
+  const uint32_t* x;         // [..][2*L2] pair rows: the ciphertexts, or the chain totals of the level below
+  const uint32_t* p;         // [..][2*L2] the running products of the forward pass, as many rows as x (may be `out`)
+  const uint32_t* u;         // [..][2*L2] the inverse of every chain's total: what the level above stored, or the uploaded row
+  const uint32_t* mul;       // [..][2*L2] as many rows as x, or null; never the same memory as out
+  const SegscanChunk* chunks;// [n_chunks], ordered by len descending; carry: a row of u
+  size_t n_chunks;           // >= 1
+  uint32_t* out;             // [..][2*L2] as many rows as x, never the same memory as x
+};
+
 // Encrypted slot packing on pair rows (hensel_pack.hpp): src read as [rows][seg_len], one Horner chain per row,
 //     out[r] = prod_t src[r][t]^(2^(slot_bits * t)):  slot 0 the least significant, one row stored per chain.
 // No descriptors: every chain of a launch has the same trip count.  The host keeps seg_len * slot_bits below the bit

@@ -332,13 +332,29 @@ inline bool launch_segsum(int G, int K, const SegsumArgs& a, unsigned blocks, hi
 }
 
 // The encrypted segmented prefix sum (hensel_segscan.hpp; k_hensel.hip parts 45-47): one product chain per chunk
-// descriptor with every intermediate row stored, in the geometries matvec_has lists (no (8,9) form: DESIGN.md section 13)
+// descriptor with every intermediate row stored, in the geometries matvec_has lists (the segment scan itself takes no
+// (8,9) form: DESIGN.md section 13; part 74 is that form for the forward pass of the batched inversion, section 22)
 bool launch_segscan_part45(int G, int K, const SegscanArgs& a, unsigned blocks, hipStream_t s);
 bool launch_segscan_part46(int G, int K, const SegscanArgs& a, unsigned blocks, hipStream_t s);
 bool launch_segscan_part47(int G, int K, const SegscanArgs& a, unsigned blocks, hipStream_t s);
+bool launch_segscan_part74(int G, int K, const SegscanArgs& a, unsigned blocks, hipStream_t s);
 inline bool launch_segscan(int G, int K, const SegscanArgs& a, unsigned blocks, hipStream_t s) {
   return launch_segscan_part45(G, K, a, blocks, s) || launch_segscan_part46(G, K, a, blocks, s) ||
-         launch_segscan_part47(G, K, a, blocks, s);
+         launch_segscan_part47(G, K, a, blocks, s) || launch_segscan_part74(G, K, a, blocks, s);
+}
+
+// The walk back of the batched inversion (hensel_invert.hpp; k_hensel.hip parts 70-73): one chain per chunk descriptor,
+// two products per entry, in the geometries matvec_has lists, and -- part 73 -- with the 72 limbs of a 2048-bit key's half
+// on 8 lanes instead of 4, as the segmented sum has it: levels that leave SIMDs empty (their forward pass: part 74)
+inline bool invert_has(int G, int K) { return matvec_has(G, K); }
+inline bool invert_wide_has(int G, int K) { return G == 8 && K == 9; }
+bool launch_invert_part70(int G, int K, const InvertArgs& a, unsigned blocks, hipStream_t s);
+bool launch_invert_part71(int G, int K, const InvertArgs& a, unsigned blocks, hipStream_t s);
+bool launch_invert_part72(int G, int K, const InvertArgs& a, unsigned blocks, hipStream_t s);
+bool launch_invert_part73(int G, int K, const InvertArgs& a, unsigned blocks, hipStream_t s);
+inline bool launch_invert(int G, int K, const InvertArgs& a, unsigned blocks, hipStream_t s) {
+  return launch_invert_part70(G, K, a, blocks, s) || launch_invert_part71(G, K, a, blocks, s) ||
+         launch_invert_part72(G, K, a, blocks, s) || launch_invert_part73(G, K, a, blocks, s);
 }
 
 // The encrypted slot packing (hensel_pack.hpp; k_hensel.hip parts 48-51): one Horner chain per output row, in the

@@ -721,6 +721,57 @@ void segscan_plan(size_t rows, size_t seg_len, int chunk, bool reverse, SegscanP
 }
 
 
+// ---- batched inversion ----
+int invert_chunk(int G, size_t m) {
+  const long forced = env_now("PGPU_INVERT_CHUNK");
+  if (forced >= 2) return (int)std::min(forced, (long)kInvertForcedMax);
+  const size_t chains = kSegscanWavesPerSimd * kSimds * (64 / (size_t)G);   // chains that fill the chip
+  return (int)std::min(kInvertForcedMax, std::max(kInvertMinChunk, m / chains));
+}
+int invert_levels(int G, size_t count) {
+  int levels = 1;
+  for (size_t m = count;; ++levels) {
+    const size_t c = (size_t)invert_chunk(G, m);
+    if (m <= c) return levels;
+    m = (m + c - 1) / c;
+  }
+}
+int invert_launches(int G, size_t count) { return count <= 1 ? 1 : 2 * invert_levels(G, count); }
+size_t invert_products(size_t count) { return count ? 3 * (count - 1) : 0; }
+bool invert_fits(int G, size_t count) {
+  const size_t c = (size_t)invert_chunk(G, count);
+  if (count > ~(size_t)0 / 3) return false;
+  return (count + c - 1) / c < (size_t)kSegscanNoCarry;
+}
+bool invert_wide_pays(int wide_G, size_t chains) {
+  const char* e = std::getenv("PGPU_INVERT_WIDE");     // (unset is not 0 here: both values force)
+  if (e && (e[0] == '0' || e[0] == '1') && !e[1]) return e[0] == '1';
+  return segsum_wide_pays(wide_G, chains);
+}
+void invert_plan(size_t count, int G, InvertPlan* plan) {
+  plan->chunk = invert_chunk(G, count);
+  plan->products = 0;
+  plan->levels.clear();
+  for (size_t m = count;;) {
+    InvertLevel lv;
+    lv.n = m;
+    lv.chunk = invert_chunk(G, m);
+    const size_t c = (size_t)lv.chunk, nch = m <= c ? 1 : (m + c - 1) / c;
+    lv.fwd.reserve(nch);
+    lv.back.reserve(nch);
+    for (size_t j = 0; j < nch; ++j) {
+      const uint32_t len = (uint32_t)std::min(c, m - j * c);
+      lv.fwd.push_back({(uint64_t)(j * c), len, kSegscanNoCarry});
+      lv.back.push_back({(uint64_t)(j * c), len, (uint32_t)j});
+    }
+    plan->products += 3 * (m - nch);
+    plan->levels.push_back(std::move(lv));
+    if (nch == 1) return;
+    m = nch;
+  }
+}
+
+
 // ---- encrypted slot packing ----
 bool pack_wide_pays(int wide_G, size_t rows) {
   const char* e = std::getenv("PGPU_PACK_WIDE");     // (unset is not 0 here: both values force)
@@ -879,6 +930,18 @@ void segscan_image(const SegscanPlan& plan, SegscanImage* out) {
     out->totals_at.push_back(out->scratch_rows);
     out->carry_at.push_back(out->scratch_rows + lv.totals);
     out->scratch_rows += 2 * lv.totals;
+  }
+}
+
+void invert_image(const InvertPlan& plan, InvertImage* out) {
+  *out = InvertImage();
+  for (size_t l = 0; l < plan.levels.size(); ++l) {
+    const InvertLevel& lv = plan.levels[l];
+    out->fwd_at.push_back(out->image.add(lv.fwd));
+    out->back_at.push_back(out->image.add(lv.back));
+    out->in_at.push_back(out->scratch_rows);
+    out->out_at.push_back(out->scratch_rows + (l ? lv.n : 0));
+    if (l) out->scratch_rows += 2 * lv.n;
   }
 }
 

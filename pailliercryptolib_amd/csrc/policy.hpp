@@ -349,6 +349,57 @@ struct SegscanPlan {
 void segscan_plan(size_t rows, size_t seg_len, int chunk, bool reverse, SegscanPlan* plan);
 
 
+// ---- the batched inversion (hensel_invert.hpp; pgpu_batch_ct_negate / _sub, pgpu_ct_negate_plan) ----
+// out[i] = x[i]^-1 mod n^2 by simultaneous inversion.  The batch is cut into chains of at most `chunk` consecutive rows;
+//   forward    segscan_kernel (no carries) stores the running products of every chain: count - chains products;
+//   recursion  the chain totals -- ceil(count / chunk) rows -- are inverted by the same procedure; a level of at most chunk
+//              rows is ONE chain, whose total the host inverts (one row down, one modular inversion, one row up);
+//   walk back  invert_walk_kernel walks every chain from the inverse of its total: 2 (len - 1) products per chain.
+// A level of m rows in k chains costs 3 (m - k) products and leaves k rows to the next one; the top level has one chain:
+// 3 (count - 1) products in all, whatever the chunk.  The chunk only trades chains in flight against levels (two launches
+// each, and the top chain is serial).
+// 1. the chunk of a level of m rows: the one that gives every SIMD kSegscanWavesPerSimd wavefronts of 64/G chains (the fill
+//    segscan_chunk aims at), m / (that many chains), at least kInvertMinChunk.  The rule is applied level by level, so a
+//    batch that fills the chip is cut into chains that just fill it, and every level that cannot fill it anyway -- all the
+//    levels above, and small batches -- is cut into pairs: there a level costs by the depth of its chains, 3 (chunk - 1)
+//    serial products, and the depth of the whole hierarchy, 3 (chunk - 1) log_chunk(count), is least at 2 (measured,
+//    tools/bench_negate.py --sweep, DESIGN.md section 22: the floor of 8 carried over from segscan_chunk took 1.5 to 1.9
+//    times the kernel time at 64 to 65536 elements).  The fill figure itself is carried over and was not swept.
+//    PGPU_INVERT_CHUNK=c, 2 <= c <= kInvertForcedMax, forces c at every level (larger values are clamped; read at every call).
+constexpr size_t kInvertMinChunk = 2;
+constexpr size_t kInvertForcedMax = kSegscanForcedMax;
+int invert_chunk(int G, size_t m);
+// 2. levels: the depth of the hierarchy -- a level of at most its chunk rows is the top.  launches: a forward pass and a
+//    walk back per level, what the timing record shows for pair-row input; count == 1 has nothing to multiply forward and
+//    is one walk back.  products: 3 (count - 1), padding excluded.
+int invert_levels(int G, size_t count);
+int invert_launches(int G, size_t count);
+size_t invert_products(size_t count);
+//    false: level 0 has more chains than the 32-bit carry field of a descriptor names, or 3 * count overflows
+bool invert_fits(int G, size_t count);
+// 3. the form of a level: the wide one (launch.hpp: invert_wide_has; 2048-bit keys: (8,9) beside (4,18)) when even 64 /
+//    wide_G chains per wavefront put at most one wavefront on a SIMD -- segsum_wide_pays' rule, carried over; measured
+//    (section 22): the wide form takes 0.71-0.75 of the base form's time at 64 to 65536 elements.
+//    PGPU_INVERT_WIDE=0 / 1 forces the base / the wide form where the key has one (read at every call).
+bool invert_wide_pays(int wide_G, size_t chains);
+// 4. the plan: levels[0] reads x and writes the result; levels[l] reads the totals of level l - 1 -- the last running
+//    product of each of its chains, in chain order -- and writes their inverses.  Execution order: forward of level 0, 1,
+//    ..., the host inversion of the top chain's total, then the walk back of the top level, ..., 1, 0.  Chain j of a level
+//    covers the rows j * chunk ... of it (only the last chain is shorter: the lists are ordered by len descending as they
+//    stand).  fwd: carry == kSegscanNoCarry; back: the same chains with carry = j, the row of the level above's output
+//    (top level: row 0 of the uploaded inverse).
+struct InvertLevel {
+  size_t n = 0;                       // rows of the level's input (and output)
+  int chunk = 0;                      // == invert_chunk(G, n)
+  std::vector<SegscanChunk> fwd, back;
+};
+struct InvertPlan {
+  int chunk = 0;                      // of level 0
+  size_t products = 0;                // == invert_products(count)
+  std::vector<InvertLevel> levels;    // size() == invert_levels(G, count)
+};
+void invert_plan(size_t count, int G, InvertPlan* plan);
+
 // ---- the encrypted slot packing (hensel_pack.hpp; pgpu_batch_ct_pack, pgpu_ct_pack_plan) ----
 // One Horner chain of (seg_len - 1) * (slot_bits + 1) products per output row, one launch, every chain equally long: there
 // is no plan but the form.  The rows are few by construction (count / seg_len), and a launch whose wavefronts leave SIMDs
@@ -508,6 +559,15 @@ struct SegscanImage {
   size_t scratch_rows = 0;
 };
 void segscan_image(const SegscanPlan& plan, SegscanImage* out);
+//   inversion     per level the forward descriptors at fwd_at[l], then the walk-back descriptors at back_at[l].  Scratch
+//                 rows: per level above the first its input (the totals of the level below, gathered) at in_at[l] and its
+//                 running products / inverses at out_at[l]  (in_at[0], out_at[0]: unused, x and the result batch)
+struct InvertImage {
+  PlanImage image;
+  std::vector<size_t> fwd_at, back_at, in_at, out_at;
+  size_t scratch_rows = 0;
+};
+void invert_image(const InvertPlan& plan, InvertImage* out);
 //   weighted sum  the row bases of the terms (tab), of the slices' results (ftab: empty without a fold), the slice
 //                 descriptors of the launch and of the fold, then their step lists
 struct WsumImage {

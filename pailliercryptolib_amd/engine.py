@@ -358,6 +358,23 @@ class PublicKey:
         return self._resident_call([self._ct(x)], count, lambda L, h, out:
                                    L.pgpu_batch_ct_segment_scan(self._h, h[0], seg_len, _capi.SCAN_REVERSE if reverse else 0, out))
 
+    def negate(self, x):
+        """Ciphertext negation: x a list of ciphertexts (ints modulo n^2) -> the list of their inverses modulo n^2, i.e.
+        encryptions of (-m) mod n, each the canonical value pow(c, -1, n^2).  One pgpu_batch_ct_negate call on resident
+        batches (all inverses from one modular inversion); there is no element-wise fall-back."""
+        if len(x) == 0:
+            raise RuntimeError("negate error: empty batch")
+        return self._resident_call([self._ct(x)], len(x), lambda L, h, out: L.pgpu_batch_ct_negate(self._h, h[0], out))
+
+    def sub(self, a, b):
+        """Ciphertext subtraction: a, b lists of ciphertexts (ints modulo n^2), b as long as a or of one element (taken
+        from every a[i]) -> the list a[i] * b[i]^-1 mod n^2, i.e. encryptions of (ma - mb) mod n.  One
+        pgpu_batch_ct_sub call on resident batches; there is no element-wise fall-back."""
+        if len(a) == 0 or len(b) not in (len(a), 1):
+            raise RuntimeError("CT - CT error: Size mismatch!")
+        return self._resident_call([self._ct(a), self._ct(b)], len(a), lambda L, h, out:
+                                   L.pgpu_batch_ct_sub(self._h, h[0], h[1], out))
+
     def pack(self, x, seg_len, slot_bits):
         """Encrypted slot packing: x a list of ciphertexts (ints modulo n^2) read as [len(x) // seg_len][seg_len] -> the
         list of len(x) // seg_len ciphertexts prod_t x[r][t]^(2^(slot_bits * t)) mod n^2, i.e. encryptions of
