@@ -20,6 +20,8 @@ CipherText sparseMatVec(const std::vector<uint64_t>& row_ptr, const std::vector<
                         const CipherText& x);
 CipherText weightedSum(const std::vector<CipherText>& xs, const PlainText& w);
 CipherText sum(const std::vector<CipherText>& xs);
+CipherText matVecSigned(const std::vector<int64_t>& w, std::size_t rows, const CipherText& x);
+CipherText matMulSigned(const std::vector<int64_t>& w, std::size_t rows, const CipherText& x, std::size_t n_vec, bool transposed);
 struct Conv2dShape;   // include/ipcl/ext/conv.hpp
 CipherText conv2d(const PlainText& w, const CipherText& x, const Conv2dShape& shape);
 // include/ipcl/ext/aggregate.hpp
@@ -71,6 +73,11 @@ class CipherText : public BaseText {
   friend CipherText ext::sum(const std::vector<CipherText>& xs);
   // prod_k xs[k][i]^w[k] (w == null: every weight 1), one weight per CipherText: csrc/host/linear.cpp
   static CipherText weightedSumMap(const std::vector<CipherText>& xs, const PlainText* w);
+  friend CipherText ext::matVecSigned(const std::vector<int64_t>& w, std::size_t rows, const CipherText& x);
+  friend CipherText ext::matMulSigned(const std::vector<int64_t>& w, std::size_t rows, const CipherText& x, std::size_t n_vec,
+                                      bool transposed);
+  // prod_j this(v, j)^w[i][j] for signed w (n_vec == 0: the matvec call, this one vector): csrc/host/linear.cpp
+  CipherText signedLinearMap(const std::vector<int64_t>& w, std::size_t rows, std::size_t n_vec, bool transposed) const;
   friend CipherText ext::conv2d(const PlainText& w, const CipherText& x, const ext::Conv2dShape& shape);
   // prod_{ci,ky,kx} this(n, ci, oy*sh + ky - ph, ox*sw + kx - pw)^w[co][ci][ky][kx]: csrc/host/conv.cpp
   CipherText convMap(const PlainText& w, const ext::Conv2dShape& shape) const;

@@ -16,6 +16,15 @@
 //                        applied to a minibatch); transposed: x read as [cols][n_vec], the result as [rows][n_vec]
 //                        (Y = W * X: a per-class gradient X^T * D).  One pgpu_batch_ct_matmul call: the matVec schedule
 //                        per output, the vectors walked in tiles whose window tables share one block.  n_vec = 1 is matVec.
+//   matVecSigned(w, rows, x) / dotSigned(w, x) / matMulSigned(w, rows, x, n_vec, transposed = false)
+//                        matVec, dot and matMul for SIGNED weights, given as int64_t: Y[i] = prod_j X[j]^w[i][j] mod n^2 with
+//                        X[j]^-1 for the negative ones, i.e. y = w * x mod n for a real linear layer, regression or filter.
+//                        One pgpu_batch_ct_matvec_signed / pgpu_batch_ct_matmul_signed call: the inverses of x from ONE
+//                        modular inversion, window tables over [x ; x^-1], Booth digits of the weights -- the cost of the
+//                        unsigned call plus three products per element, where w mod n costs a key-width exponent and
+//                        subtract(matVec(w+, x), matVec(w-, x)) two calls.  The weights travel in the smallest
+//                        two's-complement width that holds every one.  Errors like matVec's (no "negative plaintext"
+//                        one); an x that holds a non-unit modulo n^2 -- no ciphertext -- is a std::runtime_error.
 //   sparseMatVec(row_ptr, col_idx, w, x)
 //                        the same map with the plaintext matrix in CSR form, rows = row_ptr.size() - 1:
 //                        Y[i] = prod_{ row_ptr[i] <= t < row_ptr[i+1] } X[col_idx[t]]^w[t] mod n^2 -- a neighbourhood
@@ -55,6 +64,10 @@ CipherText matVec(const PlainText& w, std::size_t rows, const CipherText& x);
 CipherText dot(const PlainText& w, const CipherText& x);
 CipherText matVecBucket(const PlainText& w, std::size_t rows, const CipherText& x);
 CipherText matMul(const PlainText& w, std::size_t rows, const CipherText& x, std::size_t n_vec, bool transposed = false);
+CipherText matVecSigned(const std::vector<int64_t>& w, std::size_t rows, const CipherText& x);
+CipherText dotSigned(const std::vector<int64_t>& w, const CipherText& x);
+CipherText matMulSigned(const std::vector<int64_t>& w, std::size_t rows, const CipherText& x, std::size_t n_vec,
+                        bool transposed = false);
 CipherText sparseMatVec(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx, const PlainText& w,
                         const CipherText& x);
 CipherText weightedSum(const std::vector<CipherText>& xs, const PlainText& w);

@@ -613,6 +613,41 @@ int pgpu_batch_ct_sub(const pgpu_pubkey* key, const pgpu_batch* a, const pgpu_ba
  * than the descriptors address. */
 int pgpu_ct_negate_plan(int key_bits, size_t count, int* chunk, int* levels, int* launches, size_t* products);
 
+/* Signed-weight encrypted matrix-vector and matrix products on resident ciphertexts: pgpu_batch_ct_matvec and
+ * pgpu_batch_ct_matmul for weights that may be negative,
+ *     out[i] = prod_j x[j]^W[i][j] mod n^2,      W[i][j] a SIGNED integer in two's complement in e_bits bits
+ * (1 <= e_bits <= 64 * words(w)): bit e_bits - 1 of a stored weight is its sign, bits at and above e_bits are ignored.
+ * `w` is a plain uploaded batch of rows * cols weights, row-major; an int64 array goes in as it is (words = 1, e_bits up
+ * to 64), wider weights are multi-word two's complement.  The downloaded result is the canonical value, the product of
+ * Python's pow(x[j], W[i][j], n * n), where a negative exponent goes through pow(x[j], -1, n * n); under decryption
+ * Dec(out) = W * Dec(x) mod n.  The matmul takes n_vec vectors and the PGPU_MATMUL_TRANSPOSED flag in exactly the layouts
+ * of pgpu_batch_ct_matmul.
+ * Schedule ("Signed-weight matvec and matmul"): x^-1 by the batched inversion of pgpu_batch_ct_negate, once per
+ * call over all elements (launches of kind PGPU_KERNEL_INVERT, one host round trip); a window table of 2^w + 1 rows per
+ * element over [x ; x^-1] -- one, x^1 .. x^h, x^-1 .. x^-h, h = 2^(w-1) --, as many products to build as the unsigned
+ * table; the multi-exponentiation of the unsigned call on the radix-2^w Booth digits of the weight, as many as it has
+ * unsigned digits; the unchanged fold (kinds PGPU_KERNEL_MATVEC / PGPU_KERNEL_MATMUL).  A signed call so costs the
+ * unsigned one plus 3 * (elements - 1) products, where sub(matvec(x, W+), matvec(x, W-)) runs two of them.
+ * The refusals are those of the unsigned calls, decided on the host before any launch, *out untouched:
+ * PGPU_ERR_INVALID_PARAM for null / stale handles, size and width mismatches, e_bits outside 1 .. 64 * words(w), a matrix
+ * that is no plain uploaded batch, a batch of another key; PGPU_ERR_UNSUPPORTED for keys without pair rows, pools of more
+ * than one GPU and the masked table-gather policy (the tables are indexed by digits of the plaintext matrix).
+ * PGPU_ERR_NOT_INVERTIBLE: an element of x is no unit modulo n^2.  As for negate this ONE refusal FOLLOWS LAUNCHES (the
+ * inversion's forward passes); nothing is handed out and the lane stays usable.  There is no fall-back to another route. */
+int pgpu_batch_ct_matvec_signed(const pgpu_pubkey* key, const pgpu_batch* x, const pgpu_batch* w, size_t rows, int e_bits,
+                                pgpu_batch** out);
+int pgpu_batch_ct_matmul_signed(const pgpu_pubkey* key, const pgpu_batch* x, const pgpu_batch* w, size_t n_vec, size_t rows,
+                                int e_bits, unsigned flags, pgpu_batch** out);
+/* What the signed calls would run (host-side queries, need no device; every output pointer may be NULL): slices and tile
+ * by the unsigned rules, the window that minimises the same product count among those whose table of 2^w + 1 rows per
+ * element fits the unsigned calls' cap, table_bytes = elements of a pass * (2^w + 1) * row bytes, and products = the
+ * unsigned count + 3 * (elements of the call - 1) for the inversion.  PGPU_MATVEC_WINDOW / _SLICES and PGPU_MATMUL_WINDOW /
+ * _TILE / _SLICES force the signed calls too, read at every call.  Errors as pgpu_ct_matvec_plan / pgpu_ct_matmul_plan. */
+int pgpu_ct_matvec_signed_plan(int key_bits, size_t rows, size_t cols, int e_bits, int* window, int* slices,
+                               size_t* table_bytes, size_t* products);
+int pgpu_ct_matmul_signed_plan(int key_bits, size_t n_vec, size_t rows, size_t cols, int e_bits,
+                               int* window, int* slices, size_t* tile, size_t* table_bytes, size_t* products);
+
 /* ---- instrumentation used by bench.py (roofline) ----
  * With timing enabled every kernel launch is bracketed by two HIP events recorded on the stream
  * the kernel is launched on (no synchronisation at launch time).  pgpu_timing_collect waits for

@@ -45,6 +45,8 @@ SYMBOLS = [
     "pgpu_batch_ct_matvec_bucket", "pgpu_ct_matvec_bucket_plan",
     "pgpu_batch_ct_conv2d", "pgpu_ct_conv2d_plan",
     "pgpu_batch_ct_negate", "pgpu_batch_ct_sub", "pgpu_ct_negate_plan",
+    "pgpu_batch_ct_matvec_signed", "pgpu_ct_matvec_signed_plan",
+    "pgpu_batch_ct_matmul_signed", "pgpu_ct_matmul_signed_plan",
 ]
 FEATURE_4096_SPLIT = 1
 SEGMENT_NONE = 0xFFFFFFFF      # PGPU_SEGMENT_NONE: the element is left out of that group
@@ -206,6 +208,16 @@ def lib():
     L.pgpu_batch_ct_sub.restype = c_int
     L.pgpu_ct_negate_plan.argtypes = [c_int, c_size_t, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_size_t)]
     L.pgpu_ct_negate_plan.restype = c_int
+    L.pgpu_batch_ct_matvec_signed.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_int, POINTER(c_void_p)]
+    L.pgpu_batch_ct_matvec_signed.restype = c_int
+    L.pgpu_ct_matvec_signed_plan.argtypes = [c_int, c_size_t, c_size_t, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_size_t),
+                                             POINTER(c_size_t)]
+    L.pgpu_ct_matvec_signed_plan.restype = c_int
+    L.pgpu_batch_ct_matmul_signed.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_int, ctypes.c_uint, POINTER(c_void_p)]
+    L.pgpu_batch_ct_matmul_signed.restype = c_int
+    L.pgpu_ct_matmul_signed_plan.argtypes = [c_int, c_size_t, c_size_t, c_size_t, c_int, POINTER(c_int), POINTER(c_int),
+                                             POINTER(c_size_t), POINTER(c_size_t), POINTER(c_size_t)]
+    L.pgpu_ct_matmul_signed_plan.restype = c_int
     L.pgpu_batch_ct_segment_scan.argtypes = [c_void_p, c_void_p, c_size_t, ctypes.c_uint, POINTER(c_void_p)]
     L.pgpu_batch_ct_segment_scan.restype = c_int
     L.pgpu_ct_segment_scan_plan.argtypes = [c_int, c_size_t, c_size_t, POINTER(c_int), POINTER(c_int), POINTER(c_size_t)]

@@ -1154,3 +1154,237 @@ int pgpu_batch_ct_sub(const pgpu_pubkey* key, const pgpu_batch* a, const pgpu_ba
   RC_TRY(pair_op_launch(*r.dev, lf, pa, r.s, PGPU_KERNEL_INVERT));
   return r.finish(out);
 }
+
+// ---- signed-weight matvec and matmul (hensel_signed.hpp; policy.hpp: matvec_signed_*, matmul_signed_plan) ----
+// The two linear calls above for weights in two's complement: x^-1 by invert_batch (launches of kind PGPU_KERNEL_INVERT, one
+// host round trip, the one refusal after launches), a table of 2^w + 1 rows per element over [x ; x^-1], the
+// multi-exponentiation on Booth digits, the unchanged fold.  No other route exists: a missing kernel is an error.
+int pgpu_ct_matvec_signed_plan(int key_bits, size_t rows, size_t cols, int e_bits, int* window, int* slices, size_t* table_bytes,
+                               size_t* products) {
+  if (key_bits < 1 || rows == 0 || cols == 0 || e_bits < 1)
+    return fail(PGPU_ERR_INVALID_PARAM, "signed matvec plan: key_bits, rows, cols and e_bits must be positive");
+  int G = 0, K = 0;
+  if (!policy::matvec_geometry(key_bits, &G, &K) || !pgpu::matvec_signed_has(G, K))
+    return fail(PGPU_ERR_UNSUPPORTED, "signed matvec: keys of this size have no pair rows (1024- to 3072-bit key classes only)");
+  const size_t row_bytes = (size_t)2 * G * K * sizeof(uint32_t);
+  const size_t S = policy::matvec_slices(G, rows, cols);
+  const int w = policy::matvec_signed_window(rows, cols, e_bits, S, row_bytes);
+  const double pr = policy::matvec_signed_products(rows, cols, e_bits, w, S);
+  if (pr >= 18446744073709551615.0) return fail(PGPU_ERR_INVALID_PARAM, "signed matvec plan: the product count overflows");
+  if (window) *window = w;
+  if (slices) *slices = (int)S;
+  if (table_bytes) *table_bytes = cols * (((size_t)1 << w) + 1) * row_bytes;
+  if (products) *products = (size_t)pr;
+  return PGPU_OK;
+}
+
+int pgpu_batch_ct_matvec_signed(const pgpu_pubkey* key, const pgpu_batch* x, const pgpu_batch* w, size_t rows, int e_bits,
+                                pgpu_batch** out) {
+  RC_TRY(rt::check_ready());
+  if (!key || !x || !w || !out) return fail(PGPU_ERR_INVALID_PARAM, "null argument");
+  RC_TRY(check_gen(key->gen, "key"));
+  RC_TRY(check_gen(x->gen, "batch"));
+  RC_TRY(check_gen(w->gen, "batch"));
+  const size_t cols = x->count;
+  if (rows == 0) return fail(PGPU_ERR_INVALID_PARAM, "signed matvec error: rows must be positive");
+  if (x->words != 2 * key->n_words) return fail(PGPU_ERR_INVALID_PARAM, "signed matvec error: ciphertext width mismatch");
+  if (w->mont || w->pair_l2) return fail(PGPU_ERR_INVALID_PARAM, "signed matvec error: the matrix must be a plain uploaded batch");
+  if (rows > ~(size_t)0 / cols || w->count != rows * cols)
+    return fail(PGPU_ERR_INVALID_PARAM, "signed matvec error: Size mismatch! (the matrix must hold rows * count(x) values)");
+  if (e_bits < 1 || e_bits > 64 * w->words) return fail(PGPU_ERR_INVALID_PARAM, "signed matvec error: e_bits outside the rows of the matrix batch");
+  static const AggOp op{"signed matvec", "rows", " and this call indexes its window tables by digits of the plaintext matrix; no masked variant exists",
+                        pgpu::matvec_signed_has, "ciphertext batch belongs to a different key"};
+  const pgpu_pubkey::PubForm* pf = nullptr;
+  RC_TRY(agg_admit(op, key, &x, 1, &pf));
+  const int G = pf->H, K = pf->K;
+  const size_t LQ = (size_t)2 * G * K, row_bytes = LQ * sizeof(uint32_t);
+  const size_t S = policy::matvec_slices(G, rows, cols);
+  const int win = policy::matvec_signed_window(rows, cols, e_bits, S, row_bytes);
+  // x as pair rows, then its inverses: nothing of this call's own has been launched when the inversion refuses
+  std::unique_ptr<pgpu_batch> tx, xinv;
+  const pgpu_batch* xp = nullptr;
+  RC_TRY(as_pair_batch(key, x, &xp, &tx));
+  RC_TRY(invert_batch(key, pf, "signed matvec", xp, nullptr, xp->lane, &xinv));
+  AggRun r;
+  RC_TRY(r.open(key, pf, xp, rows));
+  RC_TRY(lanes_order(w, r.x->lane, true));
+  rt::DevMem table, partial;
+  RC_TRY(table.alloc(*r.dev, r.s, cols * (((size_t)1 << win) + 1) * row_bytes));
+  if (S > 1) RC_TRY(partial.alloc(*r.dev, r.s, S * rows * row_bytes));
+  {
+    pgpu::SignedTableArgs ta{};
+    ta.ctx = hensel_pub_view(pf, r.dev->index);
+    ta.x = r.x->prow(0);
+    ta.xinv = xinv->prow(0);
+    ta.table = (uint32_t*)table.p;
+    ta.window = win;
+    ta.elems = cols;
+    RC_TRY(timed_launch(r, 2 * cols, G, PGPU_KERNEL_MATVEC, "signed matvec", [&](unsigned blocks) { return pgpu::launch_matvec_signed_table(G, K, ta, blocks, r.s); }));
+  }
+  pgpu::MatvecArgs a{};
+  a.ctx = hensel_pub_view(pf, r.dev->index);
+  a.x = r.x->prow(0);
+  a.table = (uint32_t*)table.p;
+  a.w = w->ptr(0);
+  a.w_stride = (size_t)w->words;
+  a.w_words = w->words;
+  a.e_bits = e_bits;
+  a.window = win;
+  a.slices = (int)S;
+  a.rows = rows;
+  a.cols = cols;
+  a.out = S > 1 ? (uint32_t*)partial.p : r.o->prow(0);
+  RC_TRY(timed_launch(r, rows, G, PGPU_KERNEL_MATVEC, "signed matvec", [&](unsigned blocks) { return pgpu::launch_matvec_signed(G, K, a, blocks, r.s); }, S));
+  // the fold of pgpu_batch_ct_matvec
+  for (size_t cur = S; cur > 1;) {
+    const size_t h = (cur + 1) / 2;
+    pgpu::PairOpsArgs pa{};
+    pa.count = (cur - h) * rows;
+    const pgpu_pubkey::PubForm* lf = pair_op_form(key, pf, pa.count);
+    pa.ctx = hensel_pub_view(lf, r.dev->index);
+    pa.op = pgpu::PO_MUL;
+    pa.a = (const uint32_t*)partial.p;
+    pa.b = (const uint32_t*)partial.p + h * rows * LQ;
+    pa.b_stride = LQ;
+    pa.out = h == 1 ? r.o->prow(0) : (uint32_t*)partial.p;
+    RC_TRY(pair_op_launch(*r.dev, lf, pa, r.s, PGPU_KERNEL_MATVEC));
+    cur = h;
+  }
+  RC_TRY(lanes_order(w, r.x->lane, false));
+  return r.finish(out);
+}
+
+int pgpu_ct_matmul_signed_plan(int key_bits, size_t n_vec, size_t rows, size_t cols, int e_bits,
+                               int* window, int* slices, size_t* tile, size_t* table_bytes, size_t* products) {
+  if (key_bits < 1 || n_vec == 0 || rows == 0 || cols == 0 || e_bits < 1)
+    return fail(PGPU_ERR_INVALID_PARAM, "signed matmul plan: key_bits, n_vec, rows, cols and e_bits must be positive");
+  int G = 0, K = 0;
+  if (!policy::matvec_geometry(key_bits, &G, &K) || !pgpu::matvec_signed_has(G, K))
+    return fail(PGPU_ERR_UNSUPPORTED, "signed matmul: keys of this size have no pair rows (1024- to 3072-bit key classes only)");
+  if (cols > ~(size_t)0 / n_vec) return fail(PGPU_ERR_INVALID_PARAM, "signed matmul plan: n_vec * cols overflows");
+  const size_t row_bytes = (size_t)2 * G * K * sizeof(uint32_t);
+  policy::MatmulPlan plan;
+  policy::matmul_signed_plan(G, n_vec, rows, cols, e_bits, row_bytes, &plan);
+  if (plan.products >= 18446744073709551615.0) return fail(PGPU_ERR_INVALID_PARAM, "signed matmul plan: the product count overflows");
+  if (window) *window = plan.window;
+  if (slices) *slices = (int)plan.slices;
+  if (tile) *tile = plan.tile;
+  if (table_bytes) *table_bytes = plan.tile * cols * (((size_t)1 << plan.window) + 1) * row_bytes;
+  if (products) *products = (size_t)plan.products;
+  return PGPU_OK;
+}
+
+int pgpu_batch_ct_matmul_signed(const pgpu_pubkey* key, const pgpu_batch* x, const pgpu_batch* w, size_t n_vec, size_t rows,
+                                int e_bits, unsigned flags, pgpu_batch** out) {
+  RC_TRY(rt::check_ready());
+  if (!key || !x || !w || !out) return fail(PGPU_ERR_INVALID_PARAM, "null argument");
+  RC_TRY(check_gen(key->gen, "key"));
+  RC_TRY(check_gen(x->gen, "batch"));
+  RC_TRY(check_gen(w->gen, "batch"));
+  if (n_vec == 0 || rows == 0) return fail(PGPU_ERR_INVALID_PARAM, "signed matmul error: n_vec and rows must be positive");
+  if (x->count == 0 || x->count % n_vec != 0) return fail(PGPU_ERR_INVALID_PARAM, "signed matmul error: n_vec must divide count(x)");
+  const size_t cols = x->count / n_vec;
+  if (flags & ~PGPU_MATMUL_TRANSPOSED) return fail(PGPU_ERR_INVALID_PARAM, "signed matmul error: unknown flag bit (PGPU_MATMUL_TRANSPOSED is the only one)");
+  if (x->words != 2 * key->n_words) return fail(PGPU_ERR_INVALID_PARAM, "signed matmul error: ciphertext width mismatch");
+  if (w->mont || w->pair_l2) return fail(PGPU_ERR_INVALID_PARAM, "signed matmul error: the matrix must be a plain uploaded batch");
+  if (rows > ~(size_t)0 / cols || w->count != rows * cols)
+    return fail(PGPU_ERR_INVALID_PARAM, "signed matmul error: Size mismatch! (the matrix must hold rows * count(x) / n_vec values)");
+  if (e_bits < 1 || e_bits > 64 * w->words) return fail(PGPU_ERR_INVALID_PARAM, "signed matmul error: e_bits outside the rows of the matrix batch");
+  if (rows > ~(size_t)0 / n_vec) return fail(PGPU_ERR_INVALID_PARAM, "signed matmul error: n_vec * rows overflows");
+  static const AggOp op{"signed matmul", "vectors", " and this call indexes its window tables by digits of the plaintext matrix; no masked variant exists",
+                        pgpu::matvec_signed_has, "ciphertext batch belongs to a different key"};
+  const pgpu_pubkey::PubForm* pf = nullptr;
+  RC_TRY(agg_admit(op, key, &x, 1, &pf));
+  const int G = pf->H, K = pf->K;
+  const size_t LQ = (size_t)2 * G * K, row_bytes = LQ * sizeof(uint32_t);
+  const bool tr = (flags & PGPU_MATMUL_TRANSPOSED) != 0;
+  policy::MatmulPlan plan;
+  policy::matmul_signed_plan(G, n_vec, rows, cols, e_bits, row_bytes, &plan);
+  const int win = plan.window;
+  const size_t trows = ((size_t)1 << win) + 1;
+  const size_t S_max = std::max(plan.slices, plan.last_slices);
+  // x as pair rows, then the inverses of all n_vec * cols elements, once, before the first pass
+  std::unique_ptr<pgpu_batch> tx, xinv;
+  const pgpu_batch* xp = nullptr;
+  RC_TRY(as_pair_batch(key, x, &xp, &tx));
+  RC_TRY(invert_batch(key, pf, "signed matmul", xp, nullptr, xp->lane, &xinv));
+  AggRun r;
+  RC_TRY(r.open(key, pf, xp, n_vec * rows));
+  RC_TRY(lanes_order(w, r.x->lane, true));
+  // the blocks of pgpu_batch_ct_matmul; a staged pass of the transposed layout stages x^-1 beside x: [2][cols][t]
+  const bool staged = tr && plan.tile < n_vec;
+  rt::DevMem table, partial, stage;
+  RC_TRY(table.alloc(*r.dev, r.s, plan.tile * cols * trows * row_bytes));
+  if (S_max > 1) RC_TRY(partial.alloc(*r.dev, r.s, S_max * plan.tile * rows * row_bytes));
+  if (staged) RC_TRY(stage.alloc(*r.dev, r.s, 2 * plan.tile * cols * row_bytes));
+  for (size_t p = 0; p < plan.passes; ++p) {
+    const size_t v0 = p * plan.tile, t = p + 1 == plan.passes ? plan.last : plan.tile, n_out = t * rows;
+    const size_t S = p + 1 == plan.passes ? plan.last_slices : plan.slices;
+    const size_t x_off = tr ? v0 * LQ : v0 * cols * LQ;
+    const uint32_t *xt = r.x->prow(0) + x_off, *xit = xinv->prow(0) + x_off;
+    uint32_t* dest = tr ? r.o->prow(0) + v0 * LQ : r.o->prow(0) + v0 * rows * LQ;   // (transposed: row i of the tile at dest + i * n_vec rows)
+    if (staged) {
+      uint32_t* const s0 = (uint32_t*)stage.p;
+      uint32_t* const s1 = s0 + plan.tile * cols * LQ;
+      HIP_TRY(hipMemcpy2DAsync(s0, t * row_bytes, xt, n_vec * row_bytes, t * row_bytes, cols, hipMemcpyDeviceToDevice, r.s));
+      HIP_TRY(hipMemcpy2DAsync(s1, t * row_bytes, xit, n_vec * row_bytes, t * row_bytes, cols, hipMemcpyDeviceToDevice, r.s));
+      xt = s0;
+      xit = s1;
+    }
+    {
+      pgpu::SignedTableArgs ta{};
+      ta.ctx = hensel_pub_view(pf, r.dev->index);
+      ta.x = xt;
+      ta.xinv = xit;
+      ta.table = (uint32_t*)table.p;
+      ta.window = win;
+      ta.elems = t * cols;
+      RC_TRY(timed_launch(r, 2 * t * cols, G, PGPU_KERNEL_MATMUL, "signed matmul", [&](unsigned blocks) { return pgpu::launch_matvec_signed_table(G, K, ta, blocks, r.s); }));
+    }
+    pgpu::MatmulArgs a{};
+    a.ctx = hensel_pub_view(pf, r.dev->index);
+    a.table = (const uint32_t*)table.p;
+    a.w = w->ptr(0);
+    a.w_stride = (size_t)w->words;
+    a.w_words = w->words;
+    a.e_bits = e_bits;
+    a.window = win;
+    a.slices = (int)S;
+    a.n_out = n_out;
+    a.rows = rows;
+    a.cols = cols;
+    a.t_vec_stride = tr ? 1 : cols;
+    a.t_col_stride = tr ? t : 1;
+    if (S > 1) {          // partial products [S][t][rows], transposed [S][rows][t]
+      a.out = (uint32_t*)partial.p;
+      a.o_slice_stride = n_out;
+      a.o_vec_stride = tr ? 1 : rows;
+      a.o_row_stride = tr ? t : 1;
+    } else {              // straight into the result batch
+      a.out = dest;
+      a.o_slice_stride = 0;
+      a.o_vec_stride = tr ? 1 : rows;
+      a.o_row_stride = tr ? n_vec : 1;
+    }
+    RC_TRY(timed_launch(r, n_out, G, PGPU_KERNEL_MATMUL, "signed matmul", [&](unsigned blocks) { return pgpu::launch_matmul_signed(G, K, a, blocks, r.s); }, S));
+    // the fold of pgpu_batch_ct_matmul
+    for (size_t cur = S; cur > 1;) {
+      const size_t h = (cur + 1) / 2;
+      pgpu::PairOpsArgs pa{};
+      pa.count = (cur - h) * n_out;
+      const pgpu_pubkey::PubForm* lf = pair_op_form(key, pf, pa.count);
+      pa.ctx = hensel_pub_view(lf, r.dev->index);
+      pa.op = pgpu::PO_MUL;
+      pa.a = (const uint32_t*)partial.p;
+      pa.b = (const uint32_t*)partial.p + h * n_out * LQ;
+      pa.b_stride = LQ;
+      pa.out = h == 1 && !staged ? dest : (uint32_t*)partial.p;
+      RC_TRY(pair_op_launch(*r.dev, lf, pa, r.s, PGPU_KERNEL_MATMUL));
+      cur = h;
+    }
+    if (S > 1 && staged)
+      HIP_TRY(hipMemcpy2DAsync(dest, n_vec * row_bytes, partial.p, t * row_bytes, t * row_bytes, rows, hipMemcpyDeviceToDevice, r.s));
+  }
+  RC_TRY(lanes_order(w, r.x->lane, false));
+  return r.finish(out);
+}

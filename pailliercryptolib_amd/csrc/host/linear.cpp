@@ -1,5 +1,5 @@
-// ipcl::ext::matVec / dot / matVecBucket / matMul / sparseMatVec / weightedSum / sum -- linear maps on encrypted vectors (include/ipcl/ext/linear.hpp): one
-// pgpu_batch_ct_matvec / pgpu_batch_ct_matvec_bucket / pgpu_batch_ct_matmul / pgpu_batch_ct_spmv / pgpu_batch_ct_weighted_sum call on resident batches.  The reference composes such a map from CipherText::operator*
+// ipcl::ext::matVec / dot / matVecBucket / matMul / matVecSigned / dotSigned / matMulSigned / sparseMatVec / weightedSum / sum -- linear maps on encrypted vectors (include/ipcl/ext/linear.hpp): one
+// pgpu_batch_ct_matvec / pgpu_batch_ct_matvec_bucket / pgpu_batch_ct_matmul / pgpu_batch_ct_matvec_signed / pgpu_batch_ct_matmul_signed / pgpu_batch_ct_spmv / pgpu_batch_ct_weighted_sum call on resident batches.  The reference composes such a map from CipherText::operator*
 // (ciphertext.cpp:83-106) and operator+ (ciphertext.cpp:35-72) term by term.
 #include "ipcl/ext/linear.hpp"
 
@@ -66,6 +66,37 @@ CipherText CipherText::linearMapBatch(const PlainText& w, std::size_t rows, std:
   IPCL_GPU_CHECK(pgpu_batch_ct_matmul(m_pk->device()->h, dx->h, dw->h, n_vec, rows, ebits,
                                       transposed ? PGPU_MATMUL_TRANSPOSED : 0u, &o),
                  "matMul");
+  return CipherText(m_pk, detail::DeviceBatch::adopt(o));
+}
+
+CipherText CipherText::signedLinearMap(const std::vector<int64_t>& w, std::size_t rows, std::size_t n_vec, bool transposed) const {
+  const bool batch = n_vec != 0;
+  const char* what = batch ? "matMulSigned" : "matVecSigned";
+  ERROR_CHECK(m_size > 0, batch ? "matMulSigned error: empty CipherText" : "matVecSigned error: empty CipherText");
+  ERROR_CHECK(!batch || m_size % n_vec == 0, "matMulSigned error: Size mismatch! (n_vec must divide the CipherText)");
+  const std::size_t cols = batch ? m_size / n_vec : m_size;
+  ERROR_CHECK(rows > 0 && w.size() / rows == cols && w.size() % rows == 0,
+              batch ? "matMulSigned error: Size mismatch!" : "matVecSigned error: Size mismatch!");
+  const BigNumber& nsq = *(m_pk->getNSQ());
+  const int W = detail::words_for_bits(nsq.BitSize());
+  // the smallest two's-complement width that holds every weight: the bits of v (v >= 0) or of ~v (v < 0), and the sign
+  int ebits = 1;
+  std::vector<uint64_t> words(w.size());
+  for (std::size_t k = 0; k < w.size(); ++k) {
+    uint64_t m = (uint64_t)(w[k] < 0 ? ~w[k] : w[k]);
+    int b = 1;
+    for (; m; m >>= 1) ++b;
+    ebits = std::max(ebits, b);
+    words[k] = (uint64_t)w[k];
+  }
+  auto dx = deviceBatch(W, &nsq), dw = detail::DeviceBatch::upload(words, words.size(), 1);
+  pgpu_batch* o = nullptr;
+  if (batch)
+    IPCL_GPU_CHECK(pgpu_batch_ct_matmul_signed(m_pk->device()->h, dx->h, dw->h, n_vec, rows, ebits,
+                                               transposed ? PGPU_MATMUL_TRANSPOSED : 0u, &o),
+                   what);
+  else
+    IPCL_GPU_CHECK(pgpu_batch_ct_matvec_signed(m_pk->device()->h, dx->h, dw->h, rows, ebits, &o), what);
   return CipherText(m_pk, detail::DeviceBatch::adopt(o));
 }
 
@@ -139,6 +170,14 @@ CipherText dot(const PlainText& w, const CipherText& x) { return matVec(w, 1, x)
 CipherText matVecBucket(const PlainText& w, std::size_t rows, const CipherText& x) { return x.linearMapBucket(w, rows); }
 CipherText matMul(const PlainText& w, std::size_t rows, const CipherText& x, std::size_t n_vec, bool transposed) {
   return x.linearMapBatch(w, rows, n_vec, transposed);
+}
+CipherText matVecSigned(const std::vector<int64_t>& w, std::size_t rows, const CipherText& x) {
+  return x.signedLinearMap(w, rows, 0, false);
+}
+CipherText dotSigned(const std::vector<int64_t>& w, const CipherText& x) { return matVecSigned(w, 1, x); }
+CipherText matMulSigned(const std::vector<int64_t>& w, std::size_t rows, const CipherText& x, std::size_t n_vec, bool transposed) {
+  ERROR_CHECK(n_vec > 0, "matMulSigned error: Size mismatch! (n_vec must divide the CipherText)");
+  return x.signedLinearMap(w, rows, n_vec, transposed);
 }
 CipherText sparseMatVec(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx, const PlainText& w,
                         const CipherText& x) {

@@ -1,5 +1,5 @@
 // pailliercryptolib_amd -- instantiations of the split-form CRT-decrypt exponentiation (hensel.hpp), split over
-// PGPU_PART = 0..74 so that they compile in parallel (70-73: the walk back of the batched inversion, 74: its forward pass in the (8,9) form; 67-69: the encrypted 2-D convolution; 63-66: the bucket reduction of the bucket-method matvec; 60-62: the encrypted matrix product; 56-59: the encrypted weighted sum of K resident batches; 53-55: the encrypted sparse matrix-vector product; 38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 45-47: the encrypted segmented prefix sum; 48-51: the encrypted slot packing; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
+// PGPU_PART = 0..77 so that they compile in parallel (75-77: the signed-weight matrix-vector and matrix products; 70-73: the walk back of the batched inversion, 74: its forward pass in the (8,9) form; 67-69: the encrypted 2-D convolution; 63-66: the bucket reduction of the bucket-method matvec; 60-62: the encrypted matrix product; 56-59: the encrypted weighted sum of K resident batches; 53-55: the encrypted sparse matrix-vector product; 38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 45-47: the encrypted segmented prefix sum; 48-51: the encrypted slot packing; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
 // the two-wavefronts-per-SIMD build of the (2,19) decrypt form; 11-13: element-wise operations on pair rows).
 #include "hensel_seq.hpp"
 #include "launch.hpp"
@@ -45,9 +45,12 @@
 #if defined(PGPU_PART) && PGPU_PART >= 70 && PGPU_PART <= 73
 #include "hensel_invert.hpp"    // the batched inversion (negate / subtract): the walk back over the chains of the forward pass
 #endif
+#if defined(PGPU_PART) && PGPU_PART >= 75 && PGPU_PART <= 77
+#include "hensel_signed.hpp"    // the signed-weight matvec / matmul: a table over [x ; x^-1], Booth digits of the weights
+#endif
 
 #ifndef PGPU_PART
-#error "compile with -DPGPU_PART=0..74 (15 and 30 are retired)"
+#error "compile with -DPGPU_PART=0..77 (15 and 30 are retired)"
 #endif
 
 namespace pgpu {
@@ -708,6 +711,37 @@ bool PGPU_IV_NAME(int G, int K, const InvertArgs& a, unsigned blocks, hipStream_
   if (G != PGPU_IV_G || K != PGPU_IV_K) return false;
   if (a.mul) hipLaunchKernelGGL((invert_walk_kernel<PGPU_IV_G, PGPU_IV_K, true>), dim3(blocks), dim3(kWGThreads), 0, s, a);
   else hipLaunchKernelGGL((invert_walk_kernel<PGPU_IV_G, PGPU_IV_K, false>), dim3(blocks), dim3(kWGThreads), 0, s, a);
+  return true;
+}
+#elif PGPU_PART >= 75 && PGPU_PART <= 77
+// the signed-weight matrix-vector and matrix products (hensel_signed.hpp): table build and the two multi-exponentiations of
+// one geometry per part
+#if PGPU_PART == 75
+#define PGPU_SG_G 2
+#define PGPU_SG_K 19
+#define PGPU_SG_NAME(f) f##_part75
+#elif PGPU_PART == 76
+#define PGPU_SG_G 4
+#define PGPU_SG_K 18
+#define PGPU_SG_NAME(f) f##_part76
+#else
+#define PGPU_SG_G 8
+#define PGPU_SG_K 14
+#define PGPU_SG_NAME(f) f##_part77
+#endif
+bool PGPU_SG_NAME(launch_matvec_signed_table)(int G, int K, const SignedTableArgs& a, unsigned blocks, hipStream_t s) {
+  if (G != PGPU_SG_G || K != PGPU_SG_K) return false;
+  hipLaunchKernelGGL((matvec_signed_table_kernel<PGPU_SG_G, PGPU_SG_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
+  return true;
+}
+bool PGPU_SG_NAME(launch_matvec_signed)(int G, int K, const MatvecArgs& a, unsigned blocks, hipStream_t s) {
+  if (G != PGPU_SG_G || K != PGPU_SG_K) return false;
+  hipLaunchKernelGGL((matvec_signed_kernel<PGPU_SG_G, PGPU_SG_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
+  return true;
+}
+bool PGPU_SG_NAME(launch_matmul_signed)(int G, int K, const MatmulArgs& a, unsigned blocks, hipStream_t s) {
+  if (G != PGPU_SG_G || K != PGPU_SG_K) return false;
+  hipLaunchKernelGGL((matmul_signed_kernel<PGPU_SG_G, PGPU_SG_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
   return true;
 }
 #else

@@ -460,6 +460,19 @@ struct MatmulArgs {
   size_t o_slice_stride, o_vec_stride, o_row_stride;   // in pair rows
 };
 
+// Signed-weight matvec / matmul on pair rows (hensel_signed.hpp): the table over [x ; x^-1].  With h = 2^(window-1) an
+// element has 2h + 1 rows: row 0 = one, rows 1..h = x^1..x^h, rows h+1..2h = x^-1..x^-h.  The multi-exponentiations read
+// it through MatvecArgs / MatmulArgs as they stand (w: two's complement in e_bits bits; the table strides of MatmulArgs
+// count elements of 2h + 1 rows).
+struct SignedTableArgs {
+  HenselPubDev ctx;
+  const uint32_t* x;         // [elems][2*L2] the ciphertexts as pair rows
+  const uint32_t* xinv;      // [elems][2*L2] their inverses modulo n^2 (the batched inversion)
+  uint32_t* table;           // [elems][2^window + 1][2*L2]
+  int window;                // 1..6
+  size_t elems;              // >= 1
+};
+
 // Encrypted 2-D convolution on pair rows (hensel_conv.hpp): one pass over a TILE of whole images,
 //     out(n, co, oy, ox) = prod_{ci, ky, kx} x(n, ci, oy*sh + ky - ph, ox*sw + kx - pw)^w[co][ci][ky][kx],
 // a tap outside the image contributing one.  The table is matvec_table_kernel's, built from MatvecArgs over the tile's

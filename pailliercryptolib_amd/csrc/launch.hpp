@@ -407,6 +407,29 @@ inline bool launch_matmul(int G, int K, const MatmulArgs& a, unsigned blocks, hi
          launch_matmul_part62(G, K, a, blocks, s);
 }
 
+// The signed-weight matrix-vector and matrix products (hensel_signed.hpp; k_hensel.hip parts 75-77): the table over
+// [x ; x^-1] and the two multi-exponentiations on Booth digits of the weights, in the geometries matvec_has lists (the
+// inversion runs through launch_segscan / launch_invert, the fold through the element-wise pair products)
+inline bool matvec_signed_has(int G, int K) { return matvec_has(G, K) && invert_has(G, K); }
+#define PGPU_SIGNED_DECL(part)                                                                                        \
+  bool launch_matvec_signed_table_part##part(int G, int K, const SignedTableArgs& a, unsigned blocks, hipStream_t s); \
+  bool launch_matvec_signed_part##part(int G, int K, const MatvecArgs& a, unsigned blocks, hipStream_t s);            \
+  bool launch_matmul_signed_part##part(int G, int K, const MatmulArgs& a, unsigned blocks, hipStream_t s);
+PGPU_SIGNED_DECL(75) PGPU_SIGNED_DECL(76) PGPU_SIGNED_DECL(77)
+#undef PGPU_SIGNED_DECL
+inline bool launch_matvec_signed_table(int G, int K, const SignedTableArgs& a, unsigned blocks, hipStream_t s) {
+  return launch_matvec_signed_table_part75(G, K, a, blocks, s) || launch_matvec_signed_table_part76(G, K, a, blocks, s) ||
+         launch_matvec_signed_table_part77(G, K, a, blocks, s);
+}
+inline bool launch_matvec_signed(int G, int K, const MatvecArgs& a, unsigned blocks, hipStream_t s) {
+  return launch_matvec_signed_part75(G, K, a, blocks, s) || launch_matvec_signed_part76(G, K, a, blocks, s) ||
+         launch_matvec_signed_part77(G, K, a, blocks, s);
+}
+inline bool launch_matmul_signed(int G, int K, const MatmulArgs& a, unsigned blocks, hipStream_t s) {
+  return launch_matmul_signed_part75(G, K, a, blocks, s) || launch_matmul_signed_part76(G, K, a, blocks, s) ||
+         launch_matmul_signed_part77(G, K, a, blocks, s);
+}
+
 // The bucket reduction of the bucket-method matvec (hensel_bucket.hpp; k_hensel.hip parts 63-66): two running products
 // per chain of buckets, in the geometries matvec_has lists, and -- part 66 -- with the 72 limbs of a 2048-bit key's half
 // on 8 lanes instead of 4, as the segmented sum and the packing have it: launches that leave SIMDs empty

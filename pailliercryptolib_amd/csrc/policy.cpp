@@ -355,6 +355,60 @@ void matmul_plan(int G, size_t n_vec, size_t rows, size_t cols, int e_bits, size
 }
 
 
+// ---- signed-weight matvec and matmul ----
+// the unsigned counts (a signed table of 2h + 1 rows costs 2 (h - 1) = 2^w - 2 products, the Booth recoding has the same
+// ceil(e_bits / w) digits) plus the inversion; the table is one row longer per element, which only the cap sees
+double matvec_signed_products(size_t rows, size_t cols, int e_bits, int w, size_t slices) {
+  return matvec_products(rows, cols, e_bits, w, slices) + (double)invert_products(cols);
+}
+int matvec_signed_window(size_t rows, size_t cols, int e_bits, size_t slices, size_t row_bytes) {
+  const long forced = env_now("PGPU_MATVEC_WINDOW");
+  if (forced > 0) return (int)std::min(forced, 6L);
+  int best = 1;
+  double best_cost = matvec_products(rows, cols, e_bits, 1, slices);
+  for (int w = 2; w <= 6; ++w) {
+    if ((double)cols * (double)(((size_t)1 << w) + 1) * (double)row_bytes > (double)kMatvecTableCap) break;
+    const double cost = matvec_products(rows, cols, e_bits, w, slices);
+    if (cost < best_cost) { best_cost = cost; best = w; }
+  }
+  return best;
+}
+void matmul_signed_plan(int G, size_t n_vec, size_t rows, size_t cols, int e_bits, size_t row_bytes, MatmulPlan* plan) {
+  const long fw = env_now("PGPU_MATMUL_WINDOW"), ft = env_now("PGPU_MATMUL_TILE"), fs = env_now("PGPU_MATMUL_SLICES");
+  // tiled_plan_with over tables of 2^w + 1 rows per element
+  const int w_lo = fw > 0 ? (int)std::min(fw, 6L) : 1, w_hi = fw > 0 ? w_lo : 6;
+  int best_w = w_lo;
+  size_t best_t = ft > 0 ? std::min((size_t)ft, n_vec) : 1;
+  double best_cost = -1;
+  for (int w = w_lo; w <= w_hi; ++w) {
+    size_t t_hi = 0;
+    if (cols <= kMatvecTableCap) t_hi = std::min(n_vec, kMatvecTableCap / (cols * (((size_t)1 << w) + 1) * row_bytes));
+    if (t_hi == 0) {
+      if (w > w_lo) break;
+      t_hi = 1;     // one oversized vector: tile = 1 at the smallest window
+    }
+    size_t t_lo = 1;
+    if (ft > 0) t_lo = t_hi = std::min((size_t)ft, n_vec);
+    for (size_t t = t_hi; t >= t_lo; --t) {
+      const double cost = tiled_products_with(fs, G, n_vec, cols, rows, cols, e_bits, w, t);
+      if (best_cost < 0 || cost < best_cost || (cost == best_cost && (t > best_t || (t == best_t && w < best_w)))) {
+        best_cost = cost;
+        best_w = w;
+        best_t = t;
+      }
+    }
+  }
+  plan->window = best_w;
+  plan->tile = best_t;
+  plan->passes = (n_vec + best_t - 1) / best_t;
+  plan->last = n_vec - (plan->passes - 1) * best_t;
+  plan->slices = tiled_slices_with(fs, G, best_t, rows, cols);
+  plan->last_slices = tiled_slices_with(fs, G, plan->last, rows, cols);
+  // the one inversion runs over all n_vec * cols elements before the first pass
+  plan->products = best_cost + (double)invert_products(n_vec * cols);
+}
+
+
 // ---- encrypted 2-D convolution ----
 // the matrix product's plan with the table of an item (an image's c_in*h*w elements) apart from the terms of an output
 // (its c_in*kh*kw taps)

@@ -170,6 +170,20 @@ double matmul_products(int G, size_t n_vec, size_t rows, size_t cols, int e_bits
 void matmul_plan(int G, size_t n_vec, size_t rows, size_t cols, int e_bits, size_t row_bytes, MatmulPlan* plan);
 
 
+// ---- the signed-weight matvec and matmul (hensel_signed.hpp; pgpu_batch_ct_matvec_signed / _matmul_signed and their plans) ----
+// The two calls above for weights in two's complement: x^-1 by the batched inversion (invert_products below: 3 (E - 1) for
+// E elements, once per call), a table of 2^w + 1 rows per element over [x ; x^-1] (row 0 = one, x^1..x^h, x^-1..x^-h,
+// h = 2^(w-1): 2 (h - 1) = 2^w - 2 products, as the unsigned table), and radix-2^w Booth digits of the weights (as many as
+// unsigned digits: ceil(e_bits / w)).  So the counts are the unsigned ones plus the inversion; slices and tile rules are the
+// unsigned ones, the window minimises the same count, and only the cap sees the longer table:
+//     cols * (2^w + 1) * row_bytes <= kMatvecTableCap          (tile * cols * ... for the matmul).
+// PGPU_MATVEC_WINDOW / _SLICES and PGPU_MATMUL_WINDOW / _TILE / _SLICES force the signed calls too (read at every call).
+int matvec_signed_window(size_t rows, size_t cols, int e_bits, size_t slices, size_t row_bytes);
+double matvec_signed_products(size_t rows, size_t cols, int e_bits, int w, size_t slices);
+// plan->products includes the inversion of all n_vec * cols elements
+void matmul_signed_plan(int G, size_t n_vec, size_t rows, size_t cols, int e_bits, size_t row_bytes, MatmulPlan* plan);
+
+
 // ---- the encrypted 2-D convolution (hensel_conv.hpp; pgpu_batch_ct_conv2d, pgpu_ct_conv2d_plan) ----
 // out[n][co][oy][ox] = prod_{ci,ky,kx} x[n][ci][oy*sh + ky - ph][ox*sw + kx - pw]^w[co][ci][ky][kx] for n_img images: the
 // matrix product above with the table of an item apart from the terms of an output.  The tile is whole images per pass.

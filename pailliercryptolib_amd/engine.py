@@ -172,16 +172,31 @@ class PublicKey:
     def _ct(self, x):
         return [int(v) for v in x], 2 * self.n_words
 
-    def matvec(self, x, w, e_bits=None):
+    @staticmethod
+    def _signed_weights(flat, e_bits):
+        """(e_bits, words, two's-complement values) of signed weights; e_bits None: the smallest width holding every one"""
+        if e_bits is None:
+            e_bits = max((v if v >= 0 else ~v).bit_length() + 1 for v in flat)
+        ew = (int(e_bits) + 63) // 64
+        return int(e_bits), ew, [v & ((1 << (64 * ew)) - 1) for v in flat]
+
+    def matvec(self, x, w, e_bits=None, signed=False):
         """Encrypted matrix-vector product: x a list of ciphertexts (ints modulo n^2), w a plaintext matrix (a list of
         rows, or one flat row for a dot product) of non-negative ints -> the list of ciphertexts
         prod_j x[j]^w[i][j] mod n^2, i.e. encryptions of (w @ m) mod n.  One pgpu_batch_ct_matvec call on resident batches
-        (a shared-table multi-exponentiation); there is no element-wise fall-back."""
+        (a shared-table multi-exponentiation); there is no element-wise fall-back.
+        signed=True: the weights may be negative; they are packed as two's complement in e_bits bits (default: the smallest
+        width that holds every weight) and the one call is pgpu_batch_ct_matvec_signed (x^-1 by one batched inversion, a
+        table over [x ; x^-1], Booth digits)."""
         rows = [list(r) for r in w] if len(w) and isinstance(w[0], (list, tuple)) else [list(w)]
         cols = len(x)
         if cols == 0 or not rows or any(len(r) != cols for r in rows):
             raise RuntimeError("matvec error: Size mismatch!")
         flat = [int(v) for r in rows for v in r]
+        if signed:
+            e_bits, ew, packed = self._signed_weights(flat, e_bits)
+            return self._resident_call([self._ct(x), (packed, ew)], len(rows), lambda L, h, out:
+                                       L.pgpu_batch_ct_matvec_signed(self._h, h[0], h[1], len(rows), e_bits, out))
         if min(flat) < 0:
             raise RuntimeError("matvec error: negative weights have no encoding (pass w mod n)")
         if e_bits is None:
@@ -209,14 +224,15 @@ class PublicKey:
         return self._resident_call([self._ct(x)], len(rows), lambda L, h, out:
                                    L.pgpu_batch_ct_matvec_bucket(self._h, h[0], _ptr(wa), ew, len(rows), int(e_bits), out))
 
-    def matmul(self, x, w, transposed=False, e_bits=None):
+    def matmul(self, x, w, transposed=False, e_bits=None, signed=False):
         """Encrypted matrix product: x a list of n_vec lists of cols ciphertexts (ints modulo n^2), w a plaintext matrix
         (a list of rows of cols non-negative ints) -> a list of n_vec lists of rows ciphertexts, out[v][i] =
         prod_j x[v][j]^w[i][j] mod n^2, i.e. encryptions of (m @ w.T) mod n -- a linear layer applied to a minibatch.
         transposed: x a list of cols lists of n_vec ciphertexts, the result a list of rows lists of n_vec, out[i][v] =
         prod_j x[j][v]^w[i][j] mod n^2, i.e. encryptions of (w @ m) mod n.  One pgpu_batch_ct_matmul call on resident
         batches (the matvec's multi-exponentiation per output, the vectors walked in tiles); there is no element-wise
-        fall-back."""
+        fall-back.  signed=True: the weights may be negative, packed as for ``matvec``; one pgpu_batch_ct_matmul_signed
+        call."""
         xs, rows = [list(r) for r in x], [list(r) for r in w]
         if not xs or not xs[0] or not rows or any(len(r) != len(xs[0]) for r in xs):
             raise RuntimeError("matmul error: Size mismatch!")
@@ -224,14 +240,18 @@ class PublicKey:
         if any(len(r) != cols for r in rows):
             raise RuntimeError("matmul error: Size mismatch!")
         flat = [int(v) for r in rows for v in r]
-        if min(flat) < 0:
-            raise RuntimeError("matmul error: negative weights have no encoding (pass w mod n)")
-        if e_bits is None:
-            e_bits = max(1, max(v.bit_length() for v in flat))
-        ew = (int(e_bits) + 63) // 64
+        call = _capi.lib().pgpu_batch_ct_matmul
+        if signed:
+            e_bits, ew, flat = self._signed_weights(flat, e_bits)
+            call = _capi.lib().pgpu_batch_ct_matmul_signed
+        else:
+            if min(flat) < 0:
+                raise RuntimeError("matmul error: negative weights have no encoding (pass w mod n)")
+            if e_bits is None:
+                e_bits = max(1, max(v.bit_length() for v in flat))
+            ew = (int(e_bits) + 63) // 64
         out = self._resident_call([self._ct([c for r in xs for c in r]), (flat, ew)], n_vec * len(rows), lambda L, h, out:
-                                  L.pgpu_batch_ct_matmul(self._h, h[0], h[1], n_vec, len(rows), int(e_bits),
-                                                         1 if transposed else 0, out))
+                                  call(self._h, h[0], h[1], n_vec, len(rows), int(e_bits), 1 if transposed else 0, out))
         inner = n_vec if transposed else len(rows)
         return [out[k:k + inner] for k in range(0, len(out), inner)]
 
