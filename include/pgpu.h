@@ -240,7 +240,11 @@ int pgpu_get_table_gather_policy(void);
  *     read and write the rows without conversion (ciphertext.cpp:135-141 does a multiply and a divide per CT+CT);
  *   - other keys, plaintext rows wider than n, PGPU_PAIR_ROWS=0: Montgomery-form words c*R mod n^2 -- CT+CT one
  *     full-width Montgomery product, encrypt emits the form for free, CRT decrypt absorbs it into its load constants.
- * Operations accept any mix (plain uploaded batches included) and convert on the way in. */
+ * Operations accept any mix (plain uploaded batches included) and convert on the way in.  An uploaded ciphertext batch
+ * has 2 * n_words words and may hold values at and above n^2: the conversion on the way in runs over all 2 * n_words words,
+ * whatever the value's size, so an operation reads such a row as its value modulo n^2 (held for CT+CT, CT*PT, negate, the
+ * signed matvec / matmul and CRT decrypt at 2048 and 2051 bits; results are canonical, below n^2), and n^2
+ * itself is the non-ciphertext 0 -- pgpu_batch_ct_negate and the signed calls refuse it as PGPU_ERR_NOT_INVERTIBLE. */
 typedef struct pgpu_batch pgpu_batch;
 int pgpu_batch_create(size_t count, int words, pgpu_batch** out);            /* uninitialised */
 int pgpu_batch_upload(const uint64_t* host, size_t count, int words, size_t stride, pgpu_batch** out);

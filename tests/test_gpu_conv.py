@@ -5,14 +5,15 @@
 can still go wrong; the 240-output one under forced windows, slices (5 does not divide the 18 taps) and tiles (2: a short
 last pass).  Every reference is computed once per shape.  Further: the pgpu_batch_ct_spmv formulation of the same map on
 the same resident x, the matvec and the transposed matmul a convolution degenerates to on the same handles, edge weights,
-inputs in every form, two layers chained through CRT decrypt against torch.nn.functional.conv2d on int64 tensors, the
-refusals, the timing record, a key width off the classes and the Python layer."""
+inputs in every form, two layers chained through CRT decrypt against torch.nn.functional.conv2d on int64 tensors, a call
+whose short last pass runs on more slices than its full passes, two lanes at once, the refusals, the timing record, a key width off the classes and the Python layer."""
 import ctypes
 import json
 import os
 import random
 import subprocess
 import sys
+import threading
 
 import numpy as np
 import pytest
@@ -233,6 +234,88 @@ def test_two_chained_layers_then_decrypt(engine, knobs, bits):
         assert R.down(R.op(L.pgpu_batch_decrypt_crt, c.sk._h, y)) == [int(v) % c.n for v in t1.flatten().tolist()]
     finally:
         R.close()
+
+
+def test_last_pass_on_more_slices_than_a_full_pass(engine, knobs):
+    """3072 bits, 9 images of 11 x 11 under 8 filters of 4 x 4 -> 512 outputs per image over 16 taps, in tiles of 8, no
+    forced slices: a full pass has 4096 outputs = 512 wavefronts, fill 2 under the cap 16 / 4; the last pass of one image
+    64 wavefronts, fill 16: four slices, inside a partial block sized by the larger count.  The query of the call itself
+    reports the full passes' count; the two are read off queries with 8 images and with one.  Weights of 2 bits"""
+    bits, e_bits, tile = 3072, 2, 8
+    c = Case(engine, bits)
+    rng = random.Random(bits + 5)
+    shape = (9, 1, 11, 11, 8, 4, 4, 1, 1, 0, 0)
+    n_x, n_w, n_out = sizes(shape)
+    assert (n_out, n_w) == (9 * 512, 8 * 16)
+    ps, pt = ctypes.c_int(), ctypes.c_size_t()
+
+    def plan(n_img):
+        sh = cshape((n_img,) + shape[1:])
+        assert c.L.pgpu_ct_conv2d_plan(bits, ctypes.byref(sh), e_bits, None, ctypes.byref(ps), ctypes.byref(pt), None, None) == 0
+        return ps.value, pt.value
+    try:
+        knobs(None, tile, None)
+        full, one, whole = plan(tile), plan(1), plan(9)
+        print(f"conv2d plan, {bits} bits, tile {tile}: slices {full[0]} with {tile} images, {one[0]} with one, {whole[0]} with 9")
+        assert full == (2, tile) and one == (4, 1) and whole == (2, tile)
+        xs = [rng.randrange(1, c.nsq) for _ in range(n_x)]
+        wt = rand_filter(rng, shape, e_bits)
+        tab = [[pow(x, e, c.nsq) for e in range(4)] for x in xs]         # the weights are below 4: pow once per (x, weight)
+        want = []
+        for row in live_taps(shape):
+            acc = 1
+            for e, k in row:
+                if wt[k]:
+                    acc = acc * tab[e][wt[k]] % c.nsq
+            want.append(acc)
+        assert c.R.down(conv(c, c.R.up(xs, 2 * c.nw), c.R.up(wt, 1), shape, e_bits)) == want
+    finally:
+        c.R.close()
+
+
+def test_two_lanes_at_once(engine, knobs):
+    """two threads on different batch lanes, each with its own x and its own shape, the filters uploaded by the main thread
+    on its lane; tiles of 2 images over 3 tap slices; three calls in a row per thread, so that the blocks of one lane come
+    and go while the other's kernels run"""
+    c = Case(engine, 2048)
+    L = c.L
+    rng = random.Random(12)
+    results, errors = {}, []
+    shapes = {1: BIG, 2: SHAPES[2]}
+    wts = {lane: rand_filter(rng, sh, 13) for lane, sh in shapes.items()}
+    xss = {lane: [rng.randrange(1, c.nsq) for _ in range(sizes(sh)[0])] for lane, sh in shapes.items()}
+    knobs(None, 2, 3)
+
+    def worker(lane):
+        R = Res()
+        try:
+            R.check(L.pgpu_set_batch_lane(lane))
+            x = R.up(xss[lane], 2 * c.nw)
+            assert L.pgpu_batch_lane(x) == lane
+            for it in range(3):
+                y = R.op(L.pgpu_batch_ct_conv2d, c.pk._h, x, ws[lane], ctypes.byref(cshape(shapes[lane])), 13)
+                assert L.pgpu_batch_lane(y) == lane
+                results[(lane, it)] = R.down(y)
+        except Exception as ex:      # noqa: BLE001 -- reported by the main thread
+            errors.append((lane, repr(ex)))
+        finally:
+            R.close()
+
+    try:
+        ws = {lane: c.R.up(wts[lane], 1) for lane in shapes}         # lane of the main thread: ordered in by events
+        ts = [threading.Thread(target=worker, args=(lane,)) for lane in (1, 2)]
+        for t in ts:
+            t.start()
+        for t in ts:
+            t.join()
+        assert not errors, errors
+        assert len(results) == 6
+        for lane, sh in shapes.items():
+            want = expect(xss[lane], wts[lane], c.nsq, sh)
+            for it in range(3):
+                assert results[(lane, it)] == want, (lane, it)
+    finally:
+        c.R.close()
 
 
 def test_refusals_are_host_side(engine, knobs):

@@ -8,7 +8,8 @@ and ends in dead groups --, (7,1,9) one row, (2,17,1) one column, (40,3,4) more 
 the staged passes).  Every reference is computed once per shape and shared by both layouts: the transposed call sees the
 same matrix of ciphertexts stored the other way round.  Further: edge weights, inputs in every form, two layers chained
 through CRT decrypt, the agreement with pgpu_batch_ct_matvec (n_vec = 1) and with the pgpu_batch_ct_spmv formulation on
-the same resident x, the refusals, the timing record and the Python layer.
+the same resident x, a call whose short last pass runs on more slices than its full passes, two lanes at once, the
+refusals, the timing record and the Python layer.
 (One refusal of the header cannot be reached through the C-ABI: n_vec * rows beyond size_t needs n_vec <= count(x) and
 rows <= count(w) whose product overflows -- more elements than two batches can hold.)"""
 import ctypes
@@ -17,6 +18,7 @@ import os
 import random
 import subprocess
 import sys
+import threading
 
 import numpy as np
 import pytest
@@ -199,6 +201,93 @@ def test_equals_the_spmv_formulation(engine, knobs, bits):
         knobs()
     finally:
         R.close()
+
+
+@pytest.mark.parametrize("bits,n_vec,tile,rows,cols,s_full,s_last", [(3072, 9, 8, 512, 16, 2, 4), (2048, 9, 8, 512, 32, 4, 8),
+                                                                     (3072, 5, 3, 560, 32, 5, 8)])
+def test_last_pass_on_more_slices_than_a_full_pass(engine, knobs, bits, n_vec, tile, rows, cols, s_full, s_last):
+    """no forced slices: the short last pass runs on its own slice count (plan.last_slices) inside a partial block sized by
+    the larger of the two.  9 vectors in tiles of 8 at 3072 bits: a full pass has 4096 outputs = 512 wavefronts, fill 2 under
+    the cap 16 / 4; the last pass of one vector 64 wavefronts, fill 16: four slices.  At 2048 bits: 256 and 32 wavefronts,
+    four and eight slices of 32 columns -- the fold picks its (4,18) / (8,9) form at two counts within one call.  5 vectors
+    in tiles of 3, 70 wavefronts per vector: five slices of three vectors, then eight of two -- the short pass fills MORE of
+    the partial block than a full one.  The query of the call itself reports the full passes' count; the two counts are
+    read off queries at n_vec = tile and at the vectors of the last pass.  Weights of 2 bits keep Python's reference at
+    some 10^5 products"""
+    c = Case(engine, bits)
+    rng = random.Random(bits + 5)
+    e_bits, last = 2, n_vec % tile
+    ps, pt = ctypes.c_int(), ctypes.c_size_t()
+
+    def plan(k):
+        assert c.L.pgpu_ct_matmul_plan(bits, k, rows, cols, e_bits, None, ctypes.byref(ps), ctypes.byref(pt), None, None) == 0
+        return ps.value, pt.value
+    try:
+        knobs(None, tile, None)
+        full, one, whole = plan(tile), plan(last), plan(n_vec)
+        print(f"matmul plan, {bits} bits, tile {tile}: slices {full[0]} at n_vec = {tile}, {one[0]} at n_vec = {last}, {whole[0]} at n_vec = {n_vec}")
+        assert full == (s_full, tile) and one == (s_last, last) and whole == (s_full, tile)
+        xs = [rng.randrange(1, c.nsq) for _ in range(n_vec * cols)]
+        wm = rand_weights(rng, rows, cols, e_bits)
+        tab = [[pow(x, e, c.nsq) for e in range(4)] for x in xs]         # the weights are below 4: pow once per (x, weight)
+        want = []
+        for v in range(n_vec):
+            for row in wm:
+                acc = 1
+                for j, e in enumerate(row):
+                    if e:
+                        acc = acc * tab[v * cols + j][e] % c.nsq
+                want.append(acc)
+        both_layouts(c, c.R.up(xs, 2 * c.nw), xs, c.weights(wm, e_bits), n_vec, rows, e_bits, want, (bits,))
+    finally:
+        c.R.close()
+
+
+def test_two_lanes_at_once(engine, knobs):
+    """two threads on different batch lanes, each with its own x, the matrices uploaded by the main thread on its lane: the
+    default layout beside the transposed one, both in tiles of 2 over 3 slices (the transposed passes staged and copied
+    back); three calls in a row per thread, so that the blocks of one lane come and go while the other's kernels run"""
+    c = Case(engine, 2048)
+    L = c.L
+    rng = random.Random(12)
+    results, errors = {}, []
+    shapes = {1: (5, 6, 9), 2: (5, 5, 7)}                  # lane: n_vec, rows, cols; lane 2 stores x [cols][n_vec]
+    wms = {lane: rand_weights(rng, rows, cols, 32) for lane, (_, rows, cols) in shapes.items()}
+    xss = {lane: [rng.randrange(1, c.nsq) for _ in range(n_vec * cols)] for lane, (n_vec, _, cols) in shapes.items()}
+    knobs(None, 2, 3)
+
+    def worker(lane):
+        R = Res()
+        try:
+            R.check(L.pgpu_set_batch_lane(lane))
+            n_vec, rows, cols = shapes[lane]
+            x = R.up(xss[lane], 2 * c.nw)
+            assert L.pgpu_batch_lane(x) == lane
+            for it in range(3):
+                y = R.op(L.pgpu_batch_ct_matmul, c.pk._h, x, ws[lane], n_vec, rows, 32, TRANSPOSED if lane == 2 else 0)
+                assert L.pgpu_batch_lane(y) == lane
+                results[(lane, it)] = R.down(y)
+        except Exception as ex:      # noqa: BLE001 -- reported by the main thread
+            errors.append((lane, repr(ex)))
+        finally:
+            R.close()
+
+    try:
+        ws = {lane: c.weights(wms[lane], 32) for lane in shapes}     # lane of the main thread: ordered in by events
+        ts = [threading.Thread(target=worker, args=(lane,)) for lane in (1, 2)]
+        for t in ts:
+            t.start()
+        for t in ts:
+            t.join()
+        assert not errors, errors
+        assert len(results) == 6
+        want1 = expect(c, xss[1], wms[1], 5)
+        want2 = transpose(expect(c, transpose(xss[2], 7, 5), wms[2], 5), 5, 5)
+        for it in range(3):
+            assert results[(1, it)] == want1, it
+            assert results[(2, it)] == want2, it
+    finally:
+        c.R.close()
 
 
 def test_refusals_are_host_side(engine, knobs):

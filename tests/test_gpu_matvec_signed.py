@@ -5,12 +5,13 @@ held bit-identical to Python's pow with signed exponents (pow(x, -1, n^2) for th
 3072-bit key classes and one odd width (2051): shapes whose rows straddle a wavefront's groups and whose slices do not
 divide the columns, forced windows 1..6 and slices, weight widths across the 64-bit word boundary, edge weights, stored
 bits above e_bits, inputs in every form a resident batch can have, the agreement with sub(matvec(W+), matvec(W-)) and with
-the unsigned call, the round trip through CRT decrypt, the matmul in both layouts with a staged and a shorter last pass,
-the refusals -- the one that follows launches among them --, the timing record and the Python keyword."""
+the unsigned call, the round trip through CRT decrypt, the matmul in both layouts with a staged and a shorter last pass
+(its own depth: tests/test_gpu_matmul_signed.py), two lanes at once, the refusals -- the one that follows launches among them --, the timing record and the Python keyword."""
 import ctypes
 import json
 import os
 import random
+import threading
 
 import pytest
 
@@ -252,6 +253,61 @@ def test_matmul_both_layouts_and_staged_passes(engine, knobs, bits, n_vec):
         knobs()
         if n_vec == 1:
             assert c.R.down(c.matvec(x, w, rows, e_bits)) == flat
+    finally:
+        c.R.close()
+
+
+def test_two_lanes_at_once(engine, knobs):
+    """two threads on different batch lanes, each with its own x, the matrices uploaded by the main thread on its lane: a
+    signed matvec 17 x 40 beside a signed matmul, transposed, tile 2 and 3 slices (staged, sliced, copied back), 5 vectors
+    of 7 -> 5.  Each call blocks on the inversion's host round trip and takes up to four workspaces from its lane's arena;
+    three calls in a row per thread; one run"""
+    c = Case(engine, 2048)
+    L = c.L
+    rng = random.Random(12)
+    ref = Ref(c.nsq)
+    results, errors = {}, []
+    shapes = {1: (1, 17, 40), 2: (5, 5, 7)}                # lane: n_vec, rows, cols
+    wms = {lane: signed_matrix(rng, rows, cols, 32) for lane, (_, rows, cols) in shapes.items()}
+    xss = {lane: c.units(rng, n_vec * cols) for lane, (n_vec, _, cols) in shapes.items()}      # lane 2: stored [cols][n_vec]
+    knobs(matmul_tile=2, matmul_slices=3)
+
+    def worker(lane):
+        R = Res()
+        try:
+            R.check(L.pgpu_set_batch_lane(lane))
+            n_vec, rows, cols = shapes[lane]
+            x = R.up(xss[lane], 2 * c.nw)
+            assert L.pgpu_batch_lane(x) == lane
+            for it in range(3):
+                if lane == 1:
+                    y = R.op(L.pgpu_batch_ct_matvec_signed, c.pk._h, x, ws[lane], rows, 32)
+                else:
+                    y = R.op(L.pgpu_batch_ct_matmul_signed, c.pk._h, x, ws[lane], n_vec, rows, 32, TRANSPOSED)
+                assert L.pgpu_batch_lane(y) == lane
+                results[(lane, it)] = R.down(y)
+        except Exception as ex:      # noqa: BLE001 -- reported by the main thread
+            errors.append((lane, repr(ex)))
+        finally:
+            R.close()
+
+    try:
+        ws = {lane: c.weights(wms[lane], 32) for lane in shapes}     # lane of the main thread: ordered in by events
+        pt = ctypes.c_size_t()
+        assert L.pgpu_ct_matmul_signed_plan(2048, 5, 5, 7, 32, None, None, ctypes.byref(pt), None, None) == 0 and pt.value == 2
+        ts = [threading.Thread(target=worker, args=(lane,)) for lane in (1, 2)]
+        for t in ts:
+            t.start()
+        for t in ts:
+            t.join()
+        assert not errors, errors
+        assert len(results) == 6
+        want1 = ref.matvec(xss[1], wms[1])
+        by_vec = [ref.matvec([xss[2][j * 5 + v] for j in range(7)], wms[2]) for v in range(5)]
+        want2 = [by_vec[v][i] for i in range(5) for v in range(5)]                           # [rows][n_vec]
+        for it in range(3):
+            assert results[(1, it)] == want1, it
+            assert results[(2, it)] == want2, it
     finally:
         c.R.close()
 

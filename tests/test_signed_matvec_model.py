@@ -10,7 +10,12 @@ the CPU, in plain Python ints.
    2h + 1 rows per element over [x ; x^-1], the top-down walk per (row, column slice), the fold -- against
    prod_j pow(x_j, W_ij, n^2) with Python's signed exponents, and its executed products against the plan formula
    (csrc/policy.cpp: matvec_signed_products = the unsigned count + 3 (cols - 1)).
-3. The contract of the host-side plan queries pgpu_ct_matvec_signed_plan / pgpu_ct_matmul_signed_plan (ctypes; no device)."""
+3. The passes of pgpu_batch_ct_matmul_signed with the ADDRESSES csrc/capi_aggregate.inc and matmul_signed_kernel form, on
+   bounds-checked flat blocks for x, x^-1, stage, table, partial and out: x_off per layout, the two 2-D copies into
+   [2][tile * cols], the table of 2^w + 1 rows per element and its two strides, the output strides for one slice and for
+   several, the fold's walk and destination, the copy back with pitch n_vec, a short last pass on its own slice count --
+   every output written exactly once with the pow value, no row outside a block touched, none read before it was written.
+4. The contract of the host-side plan queries pgpu_ct_matvec_signed_plan / pgpu_ct_matmul_signed_plan (ctypes; no device)."""
 import ctypes
 import os
 import random
@@ -238,6 +243,193 @@ def test_w4_e32_against_pow():
     wm = [[rng.getrandbits(32) for _ in xs] for _ in range(8)]
     assert any(signed_value(v, 32) < 0 for r in wm for v in r)
     assert model(xs, wm, mod, 32, 4, 2)[0] == reference(xs, wm, mod, 32)
+
+
+# ---- the signed matmul's addressing ----
+class Block:
+    """a device block as a flat list of rows: every access is bounds-checked, and a row is read only after it was written"""
+
+    def __init__(self, name, rows, fill=None):
+        self.name, self.v = name, [None] * rows if fill is None else list(fill)
+        assert len(self.v) == rows
+
+    def rd(self, i):
+        assert 0 <= i < len(self.v), (self.name, "read outside the block", i, len(self.v))
+        assert self.v[i] is not None, (self.name, "read before written", i)
+        return self.v[i]
+
+    def wr(self, i, val, once=False):
+        assert 0 <= i < len(self.v), (self.name, "write outside the block", i, len(self.v))
+        assert not once or self.v[i] is None, (self.name, "written twice", i)
+        self.v[i] = val
+
+    def clear(self):
+        self.v = [None] * len(self.v)
+
+    def written(self):
+        return [i for i, r in enumerate(self.v) if r is not None]
+
+
+def copy2d(dst, d0, dpitch, src, s0, spitch, width, height, once=False):
+    """hipMemcpy2DAsync in rows: height lines of width rows, the pitches in rows too"""
+    for line in range(height):
+        for k in range(width):
+            dst.wr(d0 + line * dpitch + k, src.rd(s0 + line * spitch + k), once)
+
+
+def matmul_signed_model(xs, wm, mod, n_vec, transposed, e_bits, w, tile, slices, last_slices, g, w_words=None):
+    """the passes of pgpu_batch_ct_matmul_signed as capi_aggregate.inc sets them up, on flat blocks of rows: -> the result
+    batch.  wm: stored weights; slices / last_slices: the plan's counts for a full pass and for the last one"""
+    rows, cols = len(wm), len(xs) // n_vec
+    w_words = w_words or (e_bits + 63) // 64
+    ipw, nwin, h = 64 // g, (e_bits + w - 1) // w, 1 << (w - 1)
+    trows = (1 << w) + 1
+    passes = -(-n_vec // tile)
+    last = n_vec - (passes - 1) * tile
+    S_max = max(slices, last_slices)
+    x = Block("x", n_vec * cols, [v % mod for v in xs])
+    xinv = Block("xinv", n_vec * cols, invert_batch(xs, mod)[0])      # all n_vec * cols elements, once, before the first pass
+    out = Block("out", n_vec * rows)
+    staged = transposed and tile < n_vec
+    table = Block("table", tile * cols * trows)
+    partial = Block("partial", S_max * tile * rows) if S_max > 1 else None
+    stage = Block("stage", 2 * tile * cols) if staged else None
+    for p in range(passes):
+        v0, t = p * tile, last if p + 1 == passes else tile
+        n_out = t * rows
+        S = last_slices if p + 1 == passes else slices
+        assert 1 <= S <= cols
+        x_off = v0 if transposed else v0 * cols
+        xt, xit, xt_off, xit_off = x, xinv, x_off, x_off
+        dest = v0 if transposed else v0 * rows
+        table.clear()                             # (the model's own: a row left by an earlier pass must not be read)
+        if partial:
+            partial.clear()
+        if staged:
+            stage.clear()
+            s0 = 0
+            s1 = tile * cols
+            copy2d(stage, s0, t, x, x_off, n_vec, t, cols)
+            copy2d(stage, s1, t, xinv, x_off, n_vec, t, cols)
+            # [2][tile * cols]: the x^-1 half starts where a FULL tile of x would end, in the short last pass too
+            assert stage.written() == list(range(t * cols)) + list(range(tile * cols, tile * cols + t * cols))
+            xt, xit, xt_off, xit_off = stage, stage, s0, s1
+        for item in range(2 * t * cols):          # matvec_signed_table_kernel: one group per (element, half)
+            el, inv = item >> 1, item & 1
+            tbl = el * trows
+            base = (xit.rd(xit_off + el) if inv else xt.rd(xt_off + el))
+            if not inv:
+                table.wr(tbl, 1 % mod, once=True)
+            tbl += h if inv else 0
+            table.wr(tbl + 1, base, once=True)
+            a = base
+            for e in range(2, h + 1):
+                a = a * base % mod
+                table.wr(tbl + e, a, once=True)
+        t_vec, t_col = (1, t) if transposed else (cols, 1)
+        if S > 1:                                 # partial products [S][t][rows], transposed [S][rows][t]
+            dst, base_at, o_slice, o_vec, o_row = partial, 0, n_out, (1 if transposed else rows), (t if transposed else 1)
+        else:                                     # straight into the result batch
+            dst, base_at, o_slice, o_vec, o_row = out, dest, 0, (1 if transposed else rows), (n_vec if transposed else 1)
+        out_blocks = -(-n_out // ipw)
+        for wave in range(S * out_blocks):        # matmul_signed_kernel
+            s, blk = divmod(wave, out_blocks)
+            lo, hi = s * cols // S, (s + 1) * cols // S
+            assert lo < hi
+            for grp in range(ipw):
+                o = blk * ipw + grp
+                live = o < n_out
+                if not live:
+                    o = n_out - 1                 # dead groups of the last wavefront walk the last output
+                v, i = divmod(o, rows)
+                assert v < t
+                tvec, tcol = v * t_vec * trows, t_col * trows
+                acc = table.rd(tvec + lo * tcol + kernel_row(wm[i][lo], w_words, e_bits, w, nwin - 1))
+                for win in range(nwin - 1, -1, -1):
+                    if win != nwin - 1:
+                        for _ in range(w):
+                            acc = acc * acc % mod
+                    for j in range(lo + 1 if win == nwin - 1 else lo, hi):
+                        acc = acc * table.rd(tvec + j * tcol + kernel_row(wm[i][j], w_words, e_bits, w, win)) % mod
+                if live:
+                    dst.wr(base_at + s * o_slice + v * o_vec + i * o_row, acc, once=True)
+        cur = S                                   # the fold of pgpu_batch_ct_matmul
+        while cur > 1:
+            hh = (cur + 1) // 2
+            to, to_at = (out, dest) if hh == 1 and not staged else (partial, 0)
+            for k in range((cur - hh) * n_out):
+                to.wr(to_at + k, partial.rd(k) * partial.rd(hh * n_out + k) % mod, once=to is out)
+            cur = hh
+        if S > 1 and staged:                      # [rows][t] back into [rows][n_vec]
+            copy2d(out, dest, n_vec, partial, 0, t, t, rows, once=True)
+    assert None not in out.v                      # ... and every slot was written (once: Block.wr)
+    return out.v
+
+
+def matmul_reference(xs, wm, mod, n_vec, transposed, e_bits):
+    rows, cols = len(wm), len(xs) // n_vec
+    out = [None] * (n_vec * rows)
+    for v in range(n_vec):
+        vec = [xs[j * n_vec + v] if transposed else xs[v * cols + j] for j in range(cols)]
+        for i, y in enumerate(reference(vec, wm, mod, e_bits)):
+            out[i * n_vec + v if transposed else v * rows + i] = y
+    return out
+
+
+def unit_values(rng, count, p, q):
+    mod = (p * q) ** 2
+    xs = ([1, mod - 1] + [rng.randrange(1, mod) for _ in range(count)])[:count]
+    return [x if x % p and x % q else x + 1 for x in xs], mod
+
+
+@pytest.mark.parametrize("transposed", [False, True])
+@pytest.mark.parametrize("e_bits,w", [(13, 1), (13, 3), (13, 4), (13, 6), (32, 5), (70, 4)])
+def test_matmul_signed_model_tiles_slices_windows(e_bits, w, transposed):
+    """(5, 13, 33): tiles 1, 2 (a short last pass; transposed: staged, sliced, copied back) and 5, slices that do not divide
+    33, e_bits no multiple of w, 70 bits in two words"""
+    n_vec, rows, cols, g = 5, 13, 33, 4
+    rng = random.Random(100 * e_bits + w)
+    xs, mod = unit_values(rng, n_vec * cols, 1009, 1013)
+    wm = stored_weights(rng, rows, cols, e_bits)
+    want = matmul_reference(xs, wm, mod, n_vec, transposed, e_bits)
+    assert all(want[v if transposed else v * rows] == 1 for v in range(n_vec))      # the zero row
+    for tile in (1, 2, 5):
+        for S in (1, 2, 5, 33):
+            assert matmul_signed_model(xs, wm, mod, n_vec, transposed, e_bits, w, tile, S, S, g) == want, (tile, S)
+
+
+@pytest.mark.parametrize("transposed", [False, True])
+@pytest.mark.parametrize("n_vec,rows,cols,tile,slices,last_slices,g", [
+    (9, 6, 16, 8, 2, 4, 8),       # the shape of the GPU tests, fewer rows: one short pass of one vector on four slices
+    (9, 3, 32, 8, 4, 8, 4),
+    (5, 3, 32, 3, 5, 8, 8),       # the counts of 70 wavefronts per vector: the last pass fills more of the partial block, 8 * 2 > 5 * 3
+    (3, 5, 7, 2, 2, 5, 4),        # ... and with a last pass of one vector: 5 * 1 > 2 * 2
+    (3, 5, 7, 2, 1, 3, 2),        # no partial products in the full passes at all
+    (7, 5, 9, 2, 3, 2, 8)])       # (and the other way round)
+def test_matmul_signed_model_unequal_slices(n_vec, rows, cols, tile, slices, last_slices, g, transposed):
+    """the short last pass on its own slice count inside blocks sized for a full tile; the counts are the plan's, passed in"""
+    rng = random.Random(n_vec * 1000 + cols * 10 + last_slices)
+    xs, mod = unit_values(rng, n_vec * cols, 251, 241)
+    for e_bits, w in ((2, 1), (2, 2), (13, 4), (65, 3)):
+        wm = stored_weights(rng, rows, cols, e_bits)
+        want = matmul_reference(xs, wm, mod, n_vec, transposed, e_bits)
+        assert matmul_signed_model(xs, wm, mod, n_vec, transposed, e_bits, w, tile, slices, last_slices, g) == want, (e_bits, w)
+
+
+@pytest.mark.parametrize("g", [2, 4, 8])
+@pytest.mark.parametrize("n_vec,rows", [(1, 33), (3, 11), (2, 8), (2, 4), (7, 5), (33, 1)])
+def test_matmul_signed_model_outputs_around_a_wavefront(n_vec, rows, g):
+    """33 outputs against the 32 / 16 / 8 groups of a wavefront, one column and nine; a tile of 2 keeps v = o / rows inside
+    the tile for the clamped dead groups; weights one word wider than e_bits needs"""
+    rng = random.Random(n_vec * 100 + rows + g)
+    for cols in (1, 9):
+        xs, mod = unit_values(rng, n_vec * cols, 1009, 1013)
+        wm = [[v | (rng.getrandbits(64) << 64) for v in row] for row in stored_weights(rng, rows, cols, 32)]
+        for transposed in (False, True):
+            want = matmul_reference(xs, wm, mod, n_vec, transposed, 32)
+            for tile in sorted({min(2, n_vec), n_vec}):
+                S = min(cols, 3)
+                assert matmul_signed_model(xs, wm, mod, n_vec, transposed, 32, 4, tile, S, S, g, w_words=2) == want, (cols, tile)
 
 
 # ---- the plan queries ----
