@@ -45,8 +45,15 @@
  * is not hardened against a co-resident observer of the memory system -- unless
  * pgpu_set_table_gather_policy(1) is chosen, which makes the split-form kernels read every entry of
  * a window table and select; since round 4 that covers the DJN fixed-base product as well (a table of its own
- * with a 4-bit window: 256 products of 16 candidates each instead of 85 indexed ones).  Device copies of
- * private-key constants are zeroed before they are freed.
+ * with a 4-bit window: 256 products of 16 candidates each instead of 85 indexed ones).
+ * Under the default indexed policy the one-lane CRT-decrypt kernels keep only the odd powers of the base
+ * in the window table (PGPU_PS_ODD_TABLE, default 1): the table address already follows each digit of
+ * p-1 / q-1, and the POSITION of the multiplication inside a window then follows the digit's trailing
+ * zeros -- a subset of what the address shows.  Every window still runs w squarings and one
+ * multiplication, also for zero digits, so the duration does not depend on the key.  Under
+ * pgpu_set_table_gather_policy(1) those kernels keep the full table and the fixed order (w squarings,
+ * then the multiplication): a digit-independent instruction order.  Sliding windows stay opt-in.
+ * Device copies of private-key constants are zeroed before they are freed.
  *
  * ERRORS.  Every function returns PGPU_OK (0) or a negative pgpu_status; nothing calls
  * exit().  pgpu_last_error() returns a thread-local description.  The C++ layer turns a

@@ -1734,6 +1734,8 @@ int host_busy(rt::Device& dev, int lane, size_t count = (size_t)-1) {
 // PGPU_PS_BALANCED (default 1): the one-lane form runs on balanced limbs where the key has such a set (hensel_ps_bal.hpp);
 // 0 brings hensel_decrypt_ps_kernel of the unsigned set back
 std::atomic<int> g_ps_balanced{[] { const char* e = std::getenv("PGPU_PS_BALANCED"); return e && std::atoi(e) == 0 ? 0 : 1; }()};
+// table entries per wavefront of the last one-lane decrypt launch (pgpu_debug_last_ps_table_entries: tests see which table form ran)
+std::atomic<int> g_last_ps_table_entries{0};
 const pgpu_privkey::HenselSet* ps_balanced_set(const pgpu_privkey* key, int pair_l2) {
   return (g_ps_balanced.load() && key->hs_psb && key->hs_psb->pair_l2 == pair_l2) ? key->hs_psb.get() : nullptr;
 }
@@ -1871,7 +1873,11 @@ int decrypt_on(rt::Device& d, const pgpu_privkey* key, const uint64_t* d_c, uint
     } else if (psf) {
       const size_t lwaves = 2 * ((count + 63) / 64);
       const unsigned lblocks = (unsigned)((lwaves + pgpu::kWavesPerWG - 1) / pgpu::kWavesPerWG);
-      RC_TRY(w.table.ensure((size_t)lblocks * pgpu::kWavesPerWG * pgpu::hensel_ps_table_words(hset->K, entries) * sizeof(uint32_t), s));
+      // indexed table access: the odd powers only, 2^(w-1) + 1 entries (hensel_ps.hpp); the masked gather keeps the full table
+      h.ps_odd_table = (!h.ct_gather && policy::ps_odd_table()) ? 1 : 0;
+      const size_t pentries = pgpu::hensel_ps_table_entries(h.window, h.ps_odd_table != 0);
+      g_last_ps_table_entries.store((int)pentries);
+      RC_TRY(w.table.ensure((size_t)lblocks * pgpu::kWavesPerWG * pgpu::hensel_ps_table_words(hset->K, pentries) * sizeof(uint32_t), s));
       h.table = (uint32_t*)w.table.p;
       // a part-chip launch beside busy neighbour lanes claims whole CUs (one workgroup per CU: the launches of the lanes
       // spread over the chip, one wavefront per SIMD each)
@@ -2440,6 +2446,12 @@ int pgpu_debug_get_wave_decrypt(void) { return pgpu::policy::wave_policy(); }
 int pgpu_debug_get_ps_decrypt(void) { return pgpu::policy::ps_policy(); }
 // tests / A-B measurements: the one-lane form on balanced limbs (hensel_ps_bal.hpp) 1, on the unsigned set 0; returns what was set
 int pgpu_debug_set_ps_balanced(int on) { return g_ps_balanced.exchange(on != 0 ? 1 : 0); }
+// tests / A-B measurements: PGPU_PS_ODD_TABLE from inside the process -- the one-lane forms' odd-power window table 1, the
+// half-squared one 0; returns what was set
+int pgpu_debug_set_ps_odd_table(int on) { return pgpu::policy::set_ps_odd_table(on); }
+// ... and the window-table entries per wavefront of the last one-lane decrypt launch of this process: 2^w for the
+// half-squared table and under the masked policy, 2^(w-1) + 1 for the odd powers; 0: no such launch yet
+int pgpu_debug_last_ps_table_entries(void) { return g_last_ps_table_entries.load(); }
 // tests / A-B measurements: PGPU_FIXED_WINDOW from inside the process (1..6 forces, 0: by the rules); returns what was set
 int pgpu_debug_set_fixed_window(int w) { return pgpu::policy::set_fixed_window(w); }
 // ... and the window a CRT decrypt of that exponent length and table entry size takes (one_lane: the one-lane forms)

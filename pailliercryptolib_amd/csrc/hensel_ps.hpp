@@ -476,6 +476,20 @@ __device__ __forceinline__ void ps_exit_words(const HenselArgs& A, int side, siz
 // A.table: ps_table_words<K>(entries) 32-bit words per wavefront.
 template <int K>
 constexpr size_t ps_table_words(size_t entries) { return entries * 2 * ((K + 3) / 4) * kWave * 4; }
+// entries of a wavefront's table at window width w: the full table (half-squared; what the masked gather selects from), or
+// `one` and the 2^(w-1) odd powers
+__host__ __device__ constexpr size_t ps_table_entries(int w, bool odd) {
+  return odd ? ((size_t)1 << (w - 1)) + 1 : (size_t)1 << w;
+}
+// Where the product of a window of wl squarings stands and which entry it takes.  Odd-power table: digit d = 2^s * o, o odd, is
+// served by entry (o + 1) / 2 = base^o after wl - s squarings, the s that follow raise it to base^d; d = 0 by entry 0 = one
+// after all of them.  Full table: entry d after all wl squarings.  Every window is wl squarings and ONE product whatever its
+// digit.  Both values are the same in every lane (one side of the key, one exponent): SGPRs.
+__device__ __forceinline__ void ps_window_place(int d, int wl, bool odd, int& pos, int& idx) {
+  const int s = (odd && d) ? __builtin_ctz((unsigned)d) : 0;
+  pos = __builtin_amdgcn_readfirstlane(wl - s);
+  idx = __builtin_amdgcn_readfirstlane(odd ? ((d >> s) + 1) >> 1 : d);
+}
 
 template <int K, int LB, int MINW>
 __global__ __launch_bounds__(kWGThreads, MINW) void hensel_decrypt_ps_kernel(HenselArgs A) {
@@ -494,8 +508,11 @@ __global__ __launch_bounds__(kWGThreads, MINW) void hensel_decrypt_ps_kernel(Hen
 #pragma unroll
   for (int j = 0; j < K; ++j) n[j] = ps_uniform(HCTX(nhat)[j]);   // wave-uniform: SGPR operands of the products
   const uint32_t n1p = n[1] + 1;
-  const int w = A.window, tsize = 1 << w;
-  uint4* tw = reinterpret_cast<uint4*>(A.table + wave_id * ps_table_words<K>((size_t)tsize)) + lane;
+  const int w = A.window, tsize = 1 << w, half = tsize >> 1;
+  const bool gather = A.ct_gather != 0;
+  // the odd-power table and the product placed inside the window; the masked policy keeps the full table and the fixed order
+  const bool odd = !gather && A.ps_odd_table != 0;
+  uint4* tw = reinterpret_cast<uint4*>(A.table + wave_id * ps_table_words<K>(ps_table_entries(w, odd))) + lane;
   const uint64_t* ep = A.exp + (size_t)side * A.exp_stride;
   const int nwin = (A.exp_bits + w - 1) / w;
   auto digit = [&](int i) -> int {
@@ -505,15 +522,19 @@ __global__ __launch_bounds__(kWGThreads, MINW) void hensel_decrypt_ps_kernel(Hen
     if (sh + w > 64 && word + 1 < A.exp_words) v |= ep[word + 1] << (64 - sh);
     return (int)(v & (uint64_t)(tsize - 1));
   };
-  const bool gather = A.ct_gather != 0;
 
   // ---- c*R as a pair from the pair row of the n^2 domain (hensel_decrypt_kernel: the ct_pair entry) ----
   ps_entry_from_pair_row<K, LB>(A, side, elem, n, n1p, slot, a, b, ma, mb);
-  // ---- window table, HALF-SQUARED: entry 0 = one, entry 1 = base, entry 2k = (entry k)^2, entry 2k+1 = entry 2k times base
-  // -- 2^(w-1) - 1 pair squarings and as many pair products instead of 2^w - 2 products; a squaring costs 0.71-0.72 of a
-  // product, which also moves the best width for 1024-bit exponents from 5 to 6 bits (policy.cpp: pick_decrypt_window).  The
-  // sequence is the same for every key.  The square of the base sums what base times base summed in the chained table (2ab
-  // for ad + bc), so the bounds of that product hold for it ----
+  // ---- window table, one loop for both forms; the sequence of either is the same for every key.
+  // ODD POWERS (indexed access, the default): entry 0 = one, entry j = base^(2j-1), j = 1 .. 2^(w-1).  Trip 0 squares the base
+  // into the slot of the LAST entry; every later trip k fetches it from there as the multiplier and writes entry k+1 = entry k
+  // times base^2 -- the last trip over the slot it read.  One pair squaring and 2^(w-1) - 1 pair products, and half the table
+  // (plus one entry) of the half-squared form, whose 2^(w-1) - 1 squarings only made entries that are squares of other entries.
+  // HALF-SQUARED (masked access; PGPU_PS_ODD_TABLE=0): entry 0 = one, entry 1 = base, entry 2k = (entry k)^2, entry 2k+1 =
+  // entry 2k times base -- 2^(w-1) - 1 pair squarings and as many pair products instead of 2^w - 2 products.
+  // A squaring costs 0.71-0.72 of a product (policy.cpp: pick_decrypt_window weighs the widths by it).  The square of the base
+  // sums what base times base summed in the chained table (2ab for ad + bc), so the bounds of that product hold for it; a
+  // product by that square has the smaller operand of the two (tests/test_ps_odd_table_model.py) ----
   ps_table_store<K>(tw, 1, a, b);
   {
     uint32_t oa[K], ob[K];
@@ -524,39 +545,55 @@ __global__ __launch_bounds__(kWGThreads, MINW) void hensel_decrypt_ps_kernel(Hen
     }
     ps_table_store<K>(tw, 0, oa, ob);
   }
-  // (the base comes back from entry 1 for every product, like the entries of the main loop: held in registers across
+  // (the multiplier comes back from its entry for every product, like the entries of the main loop: held in registers across
   // the loop it cost 92 scratch accesses per product)
 #pragma unroll 1
-  for (int k = 1; 2 * k < tsize; ++k) {
-    ps_table_load<K>(a, b, tw, k, tsize, false);
-    ps_pairsqr<K, LB>(a, b, n, n1p);
-    ps_table_store<K>(tw, 2 * k, a, b);
-    __builtin_amdgcn_sched_barrier(0);      // (the base is fetched AFTER the squaring: held across it, it costs 2K registers)
-    ps_table_load<K>(ma, mb, tw, 1, tsize, false);
-    ps_pairmul<K, LB, true>(a, b, ma, mb, n, n1p, 0, slot);
-    ps_table_store<K>(tw, 2 * k + 1, a, b);
-  }
-  // ---- main loop: w squarings, one multiplication by a table entry (always, also entry 0 = one) ----
-  int win = nwin - 2;
-  if (nwin > 0) {
-    ps_table_load<K>(a, b, tw, digit(nwin - 1), tsize, gather);
-  } else {
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      a[j] = HCTX(one)[j];
-      b[j] = HCTX(one)[K + j];
+  for (int k = odd ? 0 : 1; k < half && half > 1; ++k) {
+    const bool sq = !odd || k == 0, mu = !odd || k > 0;
+    ps_table_load<K>(a, b, tw, k > 1 ? k : 1, tsize, false);
+    if (sq) {
+      ps_pairsqr<K, LB>(a, b, n, n1p);
+      ps_table_store<K>(tw, odd ? half : 2 * k, a, b);
+    }
+    __builtin_amdgcn_sched_barrier(0);      // (the multiplier is fetched AFTER the squaring: held across it, it costs 2K registers)
+    if (mu) {
+      ps_table_load<K>(ma, mb, tw, odd ? half : 1, tsize, false);
+      ps_pairmul<K, LB, true>(a, b, ma, mb, n, n1p, 0, slot);
+      ps_table_store<K>(tw, odd ? k + 1 : 2 * k + 1, a, b);
     }
   }
+  // ---- main loop: per window w squarings and one multiplication by a table entry (always, also entry 0 = one).  Half-
+  // squared form: the top digit's entry is loaded, every other window multiplies after its squarings.  Odd form: the top
+  // window is an ordinary one from `one` with the bits the exponent leaves it (A.exp_bits covers the exponent: the number of
+  // operations does not depend on it), and the product stands inside the window (ps_window_place).  ONE body of each
+  // operation, reached by wave-uniform branches ----
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    a[j] = HCTX(one)[j];
+    b[j] = HCTX(one)[K + j];
+  }
+  int win = nwin - 1;
+  if (!odd && nwin > 0) {
+    ps_table_load<K>(a, b, tw, digit(nwin - 1), tsize, gather);
+    --win;
+  }
 #pragma unroll 1
-  for (; nwin > 0 && win >= 0; --win) {
-    const int idx = digit(win);
+  for (; win >= 0; --win) {
+    const int wl = (odd && win == nwin - 1) ? A.exp_bits - win * w : w;
+    int pos, idx;
+    ps_window_place(digit(win), wl, odd, pos, idx);
 #pragma unroll 1
-    for (int i = 0; i < w; ++i) ps_pairsqr<K, LB>(a, b, n, n1p);
-    // (the entry is fetched AFTER the squarings: held across them it would cost 2K registers.  Fetching it before them in
-    // the build that owns the whole register file, and re-aligning a workgroup's wavefronts at a barrier per window or per
-    // squaring -- the unrolled code is larger than the instruction cache -- were both measured at +-0.3 %: DESIGN.md section 4)
-    ps_table_load<K>(ma, mb, tw, idx, tsize, gather);
-    ps_pairmul<K, LB, true>(a, b, ma, mb, n, n1p, 0, slot);
+    for (int i = 0; i <= wl; ++i) {
+      if (i == pos) {
+        // (the entry is fetched where it is used: held across squarings it would cost 2K registers.  Fetching it before them
+        // in the build that owns the whole register file, and re-aligning a workgroup's wavefronts at a barrier per window or
+        // per squaring -- the unrolled code is larger than the instruction cache -- were both measured at +-0.3 %: DESIGN.md
+        // section 4)
+        ps_table_load<K>(ma, mb, tw, idx, tsize, gather);
+        ps_pairmul<K, LB, true>(a, b, ma, mb, n, n1p, 0, slot);
+      }
+      if (i < wl) ps_pairsqr<K, LB>(a, b, n, n1p);
+    }
   }
   // ---- exit under the TRUE prime: (a, k*b mod p) times (hp, 0);  mp = ([a' >= p] - b') mod p ----
   ps_exit_words<K, LB>(A, side, elem, first_elem + lane < A.count, slot, a, b, ma, mb);

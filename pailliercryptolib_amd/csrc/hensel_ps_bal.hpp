@@ -343,8 +343,12 @@ __global__ __launch_bounds__(kWGThreads, MINW) void hensel_decrypt_psb_kernel(He
 #pragma unroll
   for (int j = 0; j < K; ++j) n[j] = (int32_t)ps_uniform(HCTX(nhat)[j]);   // wave-uniform: SGPR operands of the products
   const uint32_t n0inv = ps_uniform(HCTX(n0inv));
-  const int w = A.window, tsize = 1 << w;
-  uint4* tw = reinterpret_cast<uint4*>(A.table + wave_id * ps_table_words<K>((size_t)tsize)) + lane;
+  const int w = A.window, tsize = 1 << w, half = tsize >> 1;
+  const bool gather = A.ct_gather != 0;
+  // the odd-power table and the product placed inside the window (hensel_ps.hpp); the masked policy keeps the full table and
+  // the fixed order
+  const bool odd = !gather && A.ps_odd_table != 0;
+  uint4* tw = reinterpret_cast<uint4*>(A.table + wave_id * ps_table_words<K>(ps_table_entries(w, odd))) + lane;
   const uint64_t* ep = A.exp + (size_t)side * A.exp_stride;
   const int nwin = (A.exp_bits + w - 1) / w;
   auto digit = [&](int i) -> int {
@@ -354,12 +358,14 @@ __global__ __launch_bounds__(kWGThreads, MINW) void hensel_decrypt_psb_kernel(He
     if (sh + w > 64 && word + 1 < A.exp_words) v |= ep[word + 1] << (64 - sh);
     return (int)(v & (uint64_t)(tsize - 1));
   };
-  const bool gather = A.ct_gather != 0;
 
   // ---- c*R as a pair from the pair row of the n^2 domain ----
   psb_entry_from_pair_row<K, LB>(A, side, elem, n, n0inv, slot, a, b, ma, mb);
-  // ---- window table (half-squared, hensel_ps.hpp): entry 0 = one, entry 1 = base, entry 2k = (entry k)^2, entry 2k+1 =
-  // entry 2k times base.  The base leaves the entry below 2.1 p / 4.2 p, like the first product of a chained table ----
+  // ---- window table (hensel_ps.hpp), one loop for both forms.  Half-squared: entry 0 = one, entry 1 = base, entry 2k =
+  // (entry k)^2, entry 2k+1 = entry 2k times base.  Odd powers: entry j = base^(2j-1); trip 0 squares the base into the slot
+  // of the LAST entry, every later trip k fetches it from there as the multiplier and writes entry k+1 = entry k times
+  // base^2 -- the last trip over the slot it read.  The base leaves the entry below 2.1 p / 4.2 p, its square and the
+  // products by it below 0.6 p (tests/test_ps_odd_table_model.py) ----
   ps_table_store<K>(tw, 1, psb_bits<K>(a), psb_bits<K>(b));
   {
     uint32_t oa[K], ob[K];
@@ -371,33 +377,48 @@ __global__ __launch_bounds__(kWGThreads, MINW) void hensel_decrypt_psb_kernel(He
     ps_table_store<K>(tw, 0, oa, ob);
   }
 #pragma unroll 1
-  for (int k = 1; 2 * k < tsize; ++k) {
-    ps_table_load<K>(psb_bits<K>(a), psb_bits<K>(b), tw, k, tsize, false);
-    psb_pairsqr<K, LB>(a, b, n, n0inv);
-    ps_table_store<K>(tw, 2 * k, psb_bits<K>(a), psb_bits<K>(b));
-    __builtin_amdgcn_sched_barrier(0);      // (the base is fetched AFTER the squaring: held across it, it costs 2K registers)
-    ps_table_load<K>(psb_bits<K>(ma), psb_bits<K>(mb), tw, 1, tsize, false);
-    psb_pairmul<K, LB>(a, b, ma, mb, n, n0inv, slot);
-    ps_table_store<K>(tw, 2 * k + 1, psb_bits<K>(a), psb_bits<K>(b));
-  }
-  // ---- main loop: w squarings, one multiplication by a table entry (always, also entry 0 = one) ----
-  int win = nwin - 2;
-  if (nwin > 0) {
-    ps_table_load<K>(psb_bits<K>(a), psb_bits<K>(b), tw, digit(nwin - 1), tsize, gather);
-  } else {
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      a[j] = (int32_t)HCTX(one)[j];
-      b[j] = (int32_t)HCTX(one)[K + j];
+  for (int k = odd ? 0 : 1; k < half && half > 1; ++k) {
+    const bool sq = !odd || k == 0, mu = !odd || k > 0;
+    ps_table_load<K>(psb_bits<K>(a), psb_bits<K>(b), tw, k > 1 ? k : 1, tsize, false);
+    if (sq) {
+      psb_pairsqr<K, LB>(a, b, n, n0inv);
+      ps_table_store<K>(tw, odd ? half : 2 * k, psb_bits<K>(a), psb_bits<K>(b));
+    }
+    __builtin_amdgcn_sched_barrier(0);      // (the multiplier is fetched AFTER the squaring: held across it, it costs 2K registers)
+    if (mu) {
+      ps_table_load<K>(psb_bits<K>(ma), psb_bits<K>(mb), tw, odd ? half : 1, tsize, false);
+      psb_pairmul<K, LB>(a, b, ma, mb, n, n0inv, slot);
+      ps_table_store<K>(tw, odd ? k + 1 : 2 * k + 1, psb_bits<K>(a), psb_bits<K>(b));
     }
   }
+  // ---- main loop: per window w squarings and one multiplication by a table entry (always, also entry 0 = one).  Half-
+  // squared form: the top digit's entry is loaded, every other window multiplies after its squarings.  Odd form: the top
+  // window is an ordinary one from `one` with the bits the exponent leaves it (A.exp_bits covers the exponent), and the
+  // product of digit d = 2^s o follows w - s squarings (ps_window_place: wave-uniform, in SGPRs) ----
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    a[j] = (int32_t)HCTX(one)[j];
+    b[j] = (int32_t)HCTX(one)[K + j];
+  }
+  int win = nwin - 1;
+  if (!odd && nwin > 0) {
+    ps_table_load<K>(psb_bits<K>(a), psb_bits<K>(b), tw, digit(nwin - 1), tsize, gather);
+    --win;
+  }
 #pragma unroll 1
-  for (; nwin > 0 && win >= 0; --win) {
-    const int idx = digit(win);
+  for (; win >= 0; --win) {
+    const int wl = (odd && win == nwin - 1) ? A.exp_bits - win * w : w;
+    int pos, idx;
+    ps_window_place(digit(win), wl, odd, pos, idx);
 #pragma unroll 1
-    for (int i = 0; i < w; ++i) psb_pairsqr<K, LB>(a, b, n, n0inv);
-    ps_table_load<K>(psb_bits<K>(ma), psb_bits<K>(mb), tw, idx, tsize, gather);
-    psb_pairmul<K, LB>(a, b, ma, mb, n, n0inv, slot);
+    for (int i = 0; i <= wl; ++i) {
+      if (i == pos) {
+        // (the entry is fetched where it is used: held across squarings it would cost 2K registers)
+        ps_table_load<K>(psb_bits<K>(ma), psb_bits<K>(mb), tw, idx, tsize, gather);
+        psb_pairmul<K, LB>(a, b, ma, mb, n, n0inv, slot);
+      }
+      if (i < wl) psb_pairsqr<K, LB>(a, b, n, n0inv);
+    }
   }
   // ---- exit under the prime: (a, b) times (hp, 0);  mp = ([a' >= p] - [a' < 0] - b') mod p ----
   psb_exit_words<K, LB>(A, side, elem, first_elem + lane < A.count, slot, n, n0inv, a, b, ma, mb);

@@ -348,6 +348,7 @@ bool launch_hensel_psb_part52(int K, int lb, const HenselArgs& a, unsigned block
   return false;
 }
 static_assert(ps_table_words<36>(32) == 32 * 2 * ((36 + 3) / 4) * 64 * 4, "launch.hpp: hensel_ps_table_words");
+static_assert(ps_table_entries(6, true) == 33 && ps_table_entries(6, false) == 64 && ps_table_entries(1, true) == 2, "launch.hpp: hensel_ps_table_entries");
 #elif PGPU_PART == 35
 // the latency form: entry (one lane per exponentiation) -> wave kernel (one wavefront per exponentiation) -> exit; a.table is
 // the pair buffer between them (launch.hpp: hensel_wave_pair_words), the window table is dynamic LDS of the wave kernel

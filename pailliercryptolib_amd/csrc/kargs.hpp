@@ -158,7 +158,9 @@ struct HenselArgs {
   const uint64_t* exp;   // [2][exp_stride]: p-1, q-1
   size_t exp_stride;
   int exp_words;
-  int exp_bits;
+  int exp_bits;          // bit length of the longer of the two exponents: both must be below 2^exp_bits (the odd-table form
+                         //    of the one-lane kernels runs its top window over the bits this leaves it -- a set bit above
+                         //    them would lose that window's product; capi_keys.inc sets max(bits(p-1), bits(q-1)))
   int window;            // as ModexpArgs::window
   const uint16_t* sched[2];   // as ModexpArgs::sched (null: fixed-window scan)
   int sched_len[2];
@@ -173,6 +175,9 @@ struct HenselArgs {
   size_t ct_pair_stride;     // limbs per row = 2 * pair_l2
   int pair_l2;               // L2n of the rows
   int pchunk_limbs, pchunks;
+  int ps_odd_table;          // one-lane forms (hensel_ps.hpp), indexed table access only: 1 = the window table holds the odd
+                             //    powers, 2^(window-1) + 1 entries per wavefront, and a window's product follows
+                             //    window - ctz(digit) of its squarings; 0 = the half-squared table of 2^window entries
 };
 
 // Split form (hensel.hpp) of the public modulus n^2 = (n)^2: DJN encrypt with fixed-base tables of pairs.

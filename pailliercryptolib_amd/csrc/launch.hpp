@@ -283,6 +283,8 @@ inline bool launch_hensel_fb_encrypt_wave(int L2, const HenselFbArgs& a, hipStre
 }
 // 32-bit words of window table per wavefront (hensel_ps.hpp: ps_table_words -- per entry two parts of ceil(K/4) 16-byte rows of 64 lanes)
 inline size_t hensel_ps_table_words(int K, size_t entries) { return entries * 2 * (size_t)((K + 3) / 4) * 64 * 4; }
+// entries of that table at window width w (hensel_ps.hpp: ps_table_entries -- the full table, or `one` and the 2^(w-1) odd powers)
+inline size_t hensel_ps_table_entries(int w, bool odd) { return odd ? ((size_t)1 << (w - 1)) + 1 : (size_t)1 << w; }
 
 // per-element bases modulo n^2 in the same form (k_hensel.hip part 18): resident pair rows in and out, fixed window
 // (4,18): 2048-bit keys, (8,14): 3072 (part 26), (2,19): 1024 (part 28)

@@ -52,6 +52,9 @@ constexpr int kAdaptClaimBusy = 3;
 // 1 (default) for small launches of a caller that has the chip to itself, 2 always where a kernel exists (tests)
 std::atomic<int> g_wave_policy{env_int("PGPU_WAVE_FORMS", 1, 0, 2)};
 std::atomic<int> g_rr_adapt{env_int("PGPU_RR_ADAPT", 3, 0, 100)};
+// PGPU_PS_ODD_TABLE (default 1): the one-lane decrypt forms under the indexed table policy keep the ODD powers of the base only
+// and place a window's product after w - ctz(digit) of its squarings (hensel_ps.hpp); 0 brings the half-squared table back
+std::atomic<int> g_ps_odd_table{env_int("PGPU_PS_ODD_TABLE", 1, 0, 1)};
 }  // namespace
 
 int seq_policy() { return g_seq_policy.load(); }
@@ -61,6 +64,8 @@ void set_ps_policy(int p) { g_ps_policy.store(p < 0 ? 0 : (p > 2 ? 2 : p)); }
 int adapt_claim_busy() { return kAdaptClaimBusy; }
 int wave_policy() { return g_wave_policy.load(); }
 void set_wave_policy(int p) { g_wave_policy.store(p < 0 ? 0 : (p > 2 ? 2 : p)); }
+int ps_odd_table() { return g_ps_odd_table.load(); }
+int set_ps_odd_table(int on) { return g_ps_odd_table.exchange(on ? 1 : 0); }
 int rr_adapt() { return g_rr_adapt.load(); }
 int set_rr_adapt(int min_busy) { return g_rr_adapt.exchange(min_busy < 0 ? 0 : min_busy); }
 
@@ -169,17 +174,41 @@ int pick_window(int exp_bits) {
 // that stays under kDecryptTableCap -- a 65536-ciphertext launch of a 3072-bit key is 3.8 GB at w = 6 (config 4: kept), a
 // 1 M-ciphertext one would be 60 GB for a gain of 1.2 %; entry_bytes = 0: no cap (the by-exponent rule alone).
 //
-// The ONE-LANE forms (hensel_ps.hpp, hensel_ps_bal.hpp) build a half-squared table -- entry 2k = (entry k)^2, entry 2k+1 =
-// entry 2k (x) base: 2^(w-1) - 1 pair squarings and as many pair products -- and load the top digit's entry directly, so an
-// exponentiation is (nwin - 1) w + 2^(w-1) - 1 squarings and (nwin - 1) + 2^(w-1) - 1 products, and a squaring is the cheaper
-// of the two: the width is the one of the least WEIGHTED count, the weights being the instructions of the two loops of
-// hensel_decrypt_psb_kernel<36,29,1> (profiles/ps_balanced.txt; the unsigned kernels have the same ratio within 2 %:
-// 5556 / 7844).  1024-bit exponents: 1035 + 219 at w = 5, 1051 + 201 at w = 6 -- 7.04 M against 6.99 M instructions; 512
-// bits stay at 5 (3.61 M against 3.69 M), 1536 bits at 6.  The same cap holds: 8192 ciphertexts of a 2048-bit key are 302 MB at
-// w = 6.  The multi-lane forms (sequential-halves, paired, wavefront-wide) build their tables with chained products in kernels
-// of their own and keep the rule above.
+// The ONE-LANE forms (hensel_ps.hpp, hensel_ps_bal.hpp) weigh the widths: a pair squaring is the cheaper of the two operations,
+// the weights being the instructions of the two loops of hensel_decrypt_psb_kernel<36,29,1> (profiles/ps_balanced.txt; the
+// unsigned kernels have the same ratio within 2 %: 5556 / 7844).  The rule is the least weighted count of the HALF-SQUARED
+// table -- entry 2k = (entry k)^2, entry 2k+1 = entry 2k (x) base, the top digit's entry loaded directly: (nwin - 1) w +
+// 2^(w-1) - 1 squarings and (nwin - 1) + 2^(w-1) - 1 products.  1024-bit exponents: 1035 + 219 at w = 5, 1051 + 201 at w = 6 --
+// 7.04 M against 6.99 M instructions; 512 bits stay at 5 (3.61 M against 3.69 M), 1536 bits at 6.
+// The ODD-POWER table (the default under indexed access, ps_odd_table()) has other counts (ps_one_lane_ops): one squaring and
+// 2^(w-1) - 1 products build it, and every window -- the top one included, which starts from `one` -- is its bits' squarings
+// and one product: exp_bits + 1 squarings WHATEVER the width, 2^(w-1) - 1 + nwin products.  Re-weighed with them, the widths
+// of the rule above stand for every exponent class the one-lane kernels serve, so the rule is kept as it is and the width of
+// a launch does not depend on the table form:
+//   1024 bits: 1025 + 220 at w = 5, 1025 + 202 at w = 6, 1025 + 210 at w = 7 -- 6.87 M, 6.74 M, 6.80 M (5145 / 7278): 6.
+//   1536 bits: 323 products at w = 5, 287 at w = 6, 283 at w = 7: 6; the seventh bit would save 0.3 % for twice the table (the
+//     table fetch addresses 2^w entries and set_fixed_window stops at 6 as well).
+//   512 bits: 118 products at w = 5, 117 at w = 6 -- one product in 3.5 M instructions (0.2 %) for twice the table, which the
+//     window products of four lanes would then read from twice the footprint: stays at 5.
+// (Where the two counts part is below these classes: a 256-bit exponent is 71 products at w = 4 and 67 at w = 5 in the odd
+// form, 1.6 %, where the rule says 4.  tests/cpp/ps_odd_table_policy_tests.cpp holds the comparison.)
+// The cap: the sixth bit is taken while 2^6 entries of the launch stay under kDecryptTableCap.  An odd-power table of w bits
+// is as large as a full one of w - 1 bits plus one entry -- 8192 ciphertexts of a 2048-bit key are 156 MB at w = 6, 302 MB
+// half-squared -- so the cap would admit one more bit; the threshold stays where it was, for the same reason as the rule.
+// The multi-lane forms (sequential-halves, paired, wavefront-wide) build their tables with chained products in kernels of
+// their own and keep the rule above.
 constexpr size_t kDecryptTableCap = (size_t)4 << 30;
 constexpr long kPsSqrInstr = 5260, kPsMulInstr = 7278;
+void ps_one_lane_ops(int exp_bits, int w, bool odd, long* squarings, long* products) {
+  const long nwin = (exp_bits + w - 1) / w, half = 1L << (w - 1);
+  if (odd) {
+    *squarings = (half > 1 ? 1 : 0) + exp_bits;
+    *products = (half - 1) + nwin;
+  } else {
+    *squarings = (nwin - 1) * w + half - 1;
+    *products = (nwin - 1) + half - 1;
+  }
+}
 int pick_decrypt_window(int exp_bits, size_t entry_bytes, bool one_lane) {
   const int w5 = pick_window(exp_bits);
   if (g_fixed_window.load()) return w5;
@@ -188,8 +217,9 @@ int pick_decrypt_window(int exp_bits, size_t entry_bytes, bool one_lane) {
     long best_cost = 1L << 60;
     for (int w = 1; w <= 6; ++w) {
       if (w == 6 && entry_bytes > (kDecryptTableCap >> 6)) break;   // (the cap is on the sixth bit, as below)
-      const long nwin = (exp_bits + w - 1) / w, build = (1L << (w - 1)) - 1;
-      const long cost = ((nwin - 1) * w + build) * kPsSqrInstr + ((nwin - 1) + build) * kPsMulInstr;
+      long sq, mu;
+      ps_one_lane_ops(exp_bits, w, false, &sq, &mu);
+      const long cost = sq * kPsSqrInstr + mu * kPsMulInstr;
       if (cost < best_cost) { best_cost = cost; best = w; }
     }
     return best;

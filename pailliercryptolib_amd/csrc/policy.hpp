@@ -38,6 +38,8 @@ void set_ps_policy(int p);
 int adapt_claim_busy();      // up to how many busy neighbours a part-chip launch claims whole CUs (3; a constant since round 6)
 int wave_policy();           // the latency form (hensel_wave.hpp): PGPU_WAVE_FORMS: 0 never, 1 small launches while SIMDs are spare (default), 2 always
 void set_wave_policy(int p);
+int ps_odd_table();          // PGPU_PS_ODD_TABLE (hensel_ps.hpp): 1 odd-power window table of the one-lane forms (default), 0 half-squared
+int set_ps_odd_table(int on);     // returns the previous value
 int rr_adapt();              // PGPU_RR_ADAPT: from how many active neighbours on threads on round-robin lanes adapt (3; 0 never)
 int set_rr_adapt(int min_busy);   // returns the previous value
 
@@ -76,9 +78,12 @@ bool pair_mul_seq_pays(int H, int K, size_t count);
 int pick_window(int exp_bits);
 // ... of the CRT-decrypt exponentiation (a secret exponent shared by the launch): w = 6 as well from 1280 bits up
 // (entry_bytes: one table entry of every exponentiation of the launch; w = 6 only while the whole table stays under 4 GiB)
-// one_lane: the launch runs a one-lane form (hensel_ps.hpp / hensel_ps_bal.hpp: half-squared table) -- the w in 1..6 of the
-// least count weighted by the instructions of a pair squaring and a pair product: 6 from 1024-bit exponents up, same cap
+// one_lane: the launch runs a one-lane form (hensel_ps.hpp / hensel_ps_bal.hpp) -- the w in 1..6 of the least count of the
+// half-squared table weighted by the instructions of a pair squaring and a pair product: 6 from 1024-bit exponents up, same
+// cap.  The odd-power table's own counts give the same widths for 512-, 1024- and 1536-bit exponents (policy.cpp)
 int pick_decrypt_window(int exp_bits, size_t entry_bytes = 0, bool one_lane = false);
+// (pair squarings, pair products) of one exponentiation of a one-lane form at width w
+void ps_one_lane_ops(int exp_bits, int w, bool odd, long* squarings, long* products);
 // PGPU_FIXED_WINDOW from inside the process (tests): w in 1..6 forces, 0 gives the rules back; returns what was set before
 int set_fixed_window(int w);
 // ... under the masked table gather (every entry of the table read at every window product: small on purpose)

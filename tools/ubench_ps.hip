@@ -10,6 +10,10 @@
 // of ONE whole exponentiation -- table build, then nwin - 1 windows of w squarings + 1 product -- in four forms from this one
 // binary: the parent's (30 chained products, 204 x (5 + 1)), the half-squared table at w = 5 (15 x (1 + 1), 204 x (5 + 1)) and at
 // w = 6 (31 x (1 + 1), 170 x (6 + 1)), each with psb_pairsqr<K, LB, false> and <K, LB, true>; and 1020 squarings alone in both.
+// Fourth part (the odd-power window table): exp_kernel_bal<..., ODD = true> runs the decrypt kernel's odd form next to the parent's
+// in this binary -- one squaring and `build` products, then nwin windows (the top one of `half` squarings) of w squarings and one
+// product that stands after w - ctz(digit) of them, the digits a fixed pseudo-random sequence in SGPRs, the loop shape that of
+// hensel_decrypt_psb_kernel (one body of each operation, wave-uniform branches).
 // Reported in shader cycles per exponentiation (no instruction count needed).
 // build: python tools/build_ubench.py ubench_ps -I<repo>/pailliercryptolib_amd/csrc [-DPGPU_PS_SPLIT=1]   (the library's compile step, alignment pass included)
 #include <hip/hip_runtime.h>
@@ -99,7 +103,7 @@ __global__ __launch_bounds__(256, MINW) void sq_kernel_bal(const uint32_t* in, c
 
 // one exponentiation's operations on balanced limbs: `build` times ([a squaring if half] + a product), then `nwin` times
 // (w squarings + [a product if do_mul]); DBL: the pair squaring on the doubled operand
-template <int K, int LB, int MINW, bool DBL>
+template <int K, int LB, int MINW, bool DBL, bool ODD = false>
 __global__ __launch_bounds__(256, MINW) void exp_kernel_bal(const uint32_t* in, const uint32_t* nn, uint32_t* out,
                                                             unsigned long long* cyc, uint32_t n0inv_in, int build, int half,
                                                             int nwin, int w, int do_mul) {
@@ -117,6 +121,41 @@ __global__ __launch_bounds__(256, MINW) void exp_kernel_bal(const uint32_t* in, 
   }
   const uint32_t n0inv = ps_uniform(n0inv_in);
   const unsigned long long t0 = __builtin_readcyclecounter();
+  if constexpr (ODD) {
+    // `half` holds the squarings of the top window here.  Table: trip 0 squares, trips 1 .. build multiply
+#pragma unroll 1
+    for (int e = 0; e <= build; ++e) {
+      if (e == 0) psb_pairsqr<K, LB, DBL>(a, b, n, n0inv);
+      __builtin_amdgcn_sched_barrier(0);
+      if (e > 0) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+          c[j] = (int32_t)(in[(size_t)lane * 2 * K + j] ^ (e & 1));
+          d[j] = (int32_t)(in[(size_t)lane * 2 * K + K + j] ^ (e & 2));
+        }
+        psb_pairmul<K, LB>(a, b, c, d, n, n0inv, slot);
+      }
+    }
+#pragma unroll 1
+    for (int wi = 0; wi < nwin; ++wi) {
+      const int wl = wi == 0 ? half : w;
+      const int dg = (int)(((unsigned)wi * 2654435761u) >> 7) & ((1 << wl) - 1);     // digits 0 .. 2^wl - 1, every ctz
+      int pos, idx;
+      ps_window_place(dg, wl, true, pos, idx);
+#pragma unroll 1
+      for (int i = 0; i <= wl; ++i) {
+        if (i == pos) {
+#pragma unroll
+          for (int j = 0; j < K; ++j) {
+            c[j] = (int32_t)(in[(size_t)lane * 2 * K + j] ^ (idx & 1));
+            d[j] = (int32_t)(in[(size_t)lane * 2 * K + K + j] ^ (idx & 2));
+          }
+          psb_pairmul<K, LB>(a, b, c, d, n, n0inv, slot);
+        }
+        if (i < wl) psb_pairsqr<K, LB, DBL>(a, b, n, n0inv);
+      }
+    }
+  } else {
 #pragma unroll 1
   for (int e = 0; e < build; ++e) {
     if (half) psb_pairsqr<K, LB, DBL>(a, b, n, n0inv);
@@ -140,6 +179,7 @@ __global__ __launch_bounds__(256, MINW) void exp_kernel_bal(const uint32_t* in, 
       psb_pairmul<K, LB>(a, b, c, d, n, n0inv, slot);
     }
   }
+  }
   const unsigned long long t1 = __builtin_readcyclecounter();
   if (threadIdx.x % kWave == 0) cyc[lane / kWave] = t1 - t0;
 #pragma unroll
@@ -149,7 +189,7 @@ __global__ __launch_bounds__(256, MINW) void exp_kernel_bal(const uint32_t* in, 
   }
 }
 
-template <int K, int LB, bool DBL>
+template <int K, int LB, bool DBL, bool ODD = false>
 void run_exp(const char* name, int blocks, unsigned lds, int build, int half, int nwin, int w, int do_mul) {
   const size_t lanes = (size_t)blocks * 256, waves = lanes / 64;
   std::vector<uint32_t> h(lanes * 2 * K), hn(K);
@@ -166,13 +206,13 @@ void run_exp(const char* name, int blocks, unsigned lds, int build, int half, in
   hipMalloc(&din, h.size() * 4); hipMalloc(&dn, hn.size() * 4); hipMalloc(&dout, h.size() * 4); hipMalloc(&dcyc, waves * 8);
   hipMemcpy(din, h.data(), h.size() * 4, hipMemcpyHostToDevice);
   hipMemcpy(dn, hn.data(), hn.size() * 4, hipMemcpyHostToDevice);
-  if (lds) hipFuncSetAttribute((const void*)exp_kernel_bal<K, LB, 1, DBL>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+  if (lds) hipFuncSetAttribute((const void*)exp_kernel_bal<K, LB, 1, DBL, ODD>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
   hipEvent_t e0, e1;
   hipEventCreate(&e0); hipEventCreate(&e1);
   std::vector<unsigned long long> cyc(waves);
   for (int rep = 0; rep < 4; ++rep) {
     hipEventRecord(e0);
-    hipLaunchKernelGGL((exp_kernel_bal<K, LB, 1, DBL>), dim3(blocks), dim3(256), lds, 0, din, dn, dout, dcyc, n0inv, build, half, nwin, w, do_mul);
+    hipLaunchKernelGGL((exp_kernel_bal<K, LB, 1, DBL, ODD>), dim3(blocks), dim3(256), lds, 0, din, dn, dout, dcyc, n0inv, build, half, nwin, w, do_mul);
     hipEventRecord(e1);
     hipEventSynchronize(e1);
     float ms = 0;
@@ -182,7 +222,7 @@ void run_exp(const char* name, int blocks, unsigned lds, int build, int half, in
     double mean = 0;
     for (auto v : cyc) mean += (double)v;
     mean /= waves;
-    const int sq = (half ? build : 0) + nwin * w, mul = build + (do_mul ? nwin : 0);
+    const int sq = ODD ? 1 + (nwin - 1) * w + half : (half ? build : 0) + nwin * w, mul = build + (do_mul ? nwin : 0);
     if (rep) printf("%-52s doubled=%d  %4d squarings + %3d products  wall %7.3f ms | cycles per exponentiation: mean %.5g (min %.5g max %.5g)"
                     " | clock held %.3f GHz\n", name, (int)DBL, sq, mul, ms, mean, (double)cyc.front(), (double)cyc.back(),
                     (double)cyc.back() / (ms * 1e6));
@@ -272,6 +312,11 @@ int main(int argc, char** argv) {
   run_exp<36, 29, true>("w=5, chained table (30 products)", 64, 84000, 30, 0, 204, 5, 1);
   run_exp<36, 29, true>("w=5, half-squared table", 64, 84000, 15, 1, 204, 5, 1);
   run_exp<36, 29, true>("w=6, half-squared table", 64, 84000, 31, 1, 170, 6, 1);
+  // the odd-power table: 1 squaring + 31 products, 171 windows (the top one of 4 bits) with the product inside; its parent beside it
+  run_exp<36, 29, true, true>("w=6, odd-power table, product inside the window", 64, 84000, 31, 4, 171, 6, 1);
+  run_exp<36, 29, true>("w=6, half-squared table (parent of the odd form)", 64, 84000, 31, 1, 170, 6, 1);
+  run_exp<36, 29, true, true>("w=6, odd-power table, product inside the window", 64, 84000, 31, 4, 171, 6, 1);
+  run_exp<36, 29, true>("w=6, half-squared table (parent of the odd form)", 64, 84000, 31, 1, 170, 6, 1);
   run_exp<36, 29, false>("squarings alone", 64, 84000, 0, 0, 170, 6, 0);
   run_exp<36, 29, true>("squarings alone", 64, 84000, 0, 0, 170, 6, 0);
   run_exp<36, 29, false>("parent again: w=5, chained table (30 products)", 64, 84000, 30, 0, 204, 5, 1);
