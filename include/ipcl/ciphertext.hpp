@@ -22,8 +22,11 @@ CipherText weightedSum(const std::vector<CipherText>& xs, const PlainText& w);
 CipherText sum(const std::vector<CipherText>& xs);
 CipherText matVecSigned(const std::vector<int64_t>& w, std::size_t rows, const CipherText& x);
 CipherText matMulSigned(const std::vector<int64_t>& w, std::size_t rows, const CipherText& x, std::size_t n_vec, bool transposed);
+CipherText sparseMatVecSigned(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx,
+                              const std::vector<int64_t>& w, const CipherText& x);
 struct Conv2dShape;   // include/ipcl/ext/conv.hpp
 CipherText conv2d(const PlainText& w, const CipherText& x, const Conv2dShape& shape);
+CipherText conv2dSigned(const std::vector<int64_t>& w, const CipherText& x, const Conv2dShape& shape);
 // include/ipcl/ext/aggregate.hpp
 CipherText segmentSum(const CipherText& x, const std::vector<uint32_t>& ids, std::size_t n_segments, std::size_t groups);
 CipherText segmentScan(const CipherText& x, std::size_t seg_len, bool reverse);
@@ -78,7 +81,15 @@ class CipherText : public BaseText {
                                       bool transposed);
   // prod_j this(v, j)^w[i][j] for signed w (n_vec == 0: the matvec call, this one vector): csrc/host/linear.cpp
   CipherText signedLinearMap(const std::vector<int64_t>& w, std::size_t rows, std::size_t n_vec, bool transposed) const;
+  friend CipherText ext::sparseMatVecSigned(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx,
+                                            const std::vector<int64_t>& w, const CipherText& x);
+  // prod_t this[col_idx[t]]^w[t] over the CSR entries t of every row, for signed w: csrc/host/linear.cpp
+  CipherText signedSparseLinearMap(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx,
+                                   const std::vector<int64_t>& w) const;
   friend CipherText ext::conv2d(const PlainText& w, const CipherText& x, const ext::Conv2dShape& shape);
+  friend CipherText ext::conv2dSigned(const std::vector<int64_t>& w, const CipherText& x, const ext::Conv2dShape& shape);
+  // the same for signed w: csrc/host/conv.cpp
+  CipherText signedConvMap(const std::vector<int64_t>& w, const ext::Conv2dShape& shape) const;
   // prod_{ci,ky,kx} this(n, ci, oy*sh + ky - ph, ox*sw + kx - pw)^w[co][ci][ky][kx]: csrc/host/conv.cpp
   CipherText convMap(const PlainText& w, const ext::Conv2dShape& shape) const;
   friend CipherText ext::segmentSum(const CipherText& x, const std::vector<uint32_t>& ids, std::size_t n_segments,

@@ -13,6 +13,15 @@
 //                        replicated weights (what sparseMatVec of linear.hpp needs for the same map).
 //   conv1d(w, x, n_seq, c_in, len, c_out, k, stride = 1, pad = 0)
 //                        the h = kh = 1 case: x read as [n_seq][c_in][len], w as [c_out][c_in][k]
+//   conv2dSigned(w, x, shape) / conv1dSigned(w, x, n_seq, c_in, len, c_out, k, stride = 1, pad = 0)
+//                        conv2d and conv1d for SIGNED filters, given as int64_t in the same [c_out][c_in][kh][kw] order:
+//                        X^-1 for the negative taps, i.e. the cross-correlation with a real CNN filter, mod n.  One
+//                        pgpu_batch_ct_conv2d_signed call: the inverses of x from ONE modular inversion, window tables
+//                        over [x ; x^-1], Booth digits of the filters -- the cost of conv2d plus three products per
+//                        pixel, where w mod n costs a key-width exponent and subtract(conv2d(w+, x), conv2d(w-, x)) two
+//                        calls.  The filters travel in the smallest two's-complement width that holds every tap.  Errors
+//                        like conv2d's (no "negative plaintext" one); an x that holds a non-unit modulo n^2 -- no
+//                        ciphertext -- is a std::runtime_error.
 //
 // Sum pooling is a reshape by the caller: n_img' = n_img*c, c_in = c_out = 1, all-ones taps, stride equal to the kernel.
 // Not offered: dilation, groups, a bias (add it with CipherText::operator+(PlainText)), tiling inside one image.
@@ -24,6 +33,8 @@
 #define PAILLIERCRYPTOLIB_AMD_IPCL_EXT_CONV_HPP_
 
 #include <cstddef>
+#include <cstdint>
+#include <vector>
 
 #include "ipcl/ciphertext.hpp"
 #include "ipcl/plaintext.hpp"
@@ -41,6 +52,9 @@ struct Conv2dShape {
 CipherText conv2d(const PlainText& w, const CipherText& x, const Conv2dShape& shape);
 CipherText conv1d(const PlainText& w, const CipherText& x, std::size_t n_seq, std::size_t c_in, std::size_t len,
                   std::size_t c_out, std::size_t k, std::size_t stride = 1, std::size_t pad = 0);
+CipherText conv2dSigned(const std::vector<int64_t>& w, const CipherText& x, const Conv2dShape& shape);
+CipherText conv1dSigned(const std::vector<int64_t>& w, const CipherText& x, std::size_t n_seq, std::size_t c_in, std::size_t len,
+                        std::size_t c_out, std::size_t k, std::size_t stride = 1, std::size_t pad = 0);
 
 }  // namespace ext
 }  // namespace ipcl

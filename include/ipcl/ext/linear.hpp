@@ -34,6 +34,13 @@
 //                        column named twice contributes twice, an empty row yields an encryption of 0 (the ciphertext 1).
 //                        One pgpu_batch_ct_spmv call: the window tables of the x[j] shared by all rows, the squarings
 //                        shared by the terms of a chain of a row.
+//   sparseMatVecSigned(row_ptr, col_idx, w, x)
+//                        sparseMatVec for SIGNED weights, given as int64_t in CSR order (a graph Laplacian, a pruned layer):
+//                        X[col_idx[t]]^-1 for the negative ones; a column named twice with weights a and -a contributes
+//                        nothing.  One pgpu_batch_ct_spmv_signed call: the inverses of ALL of x from one modular
+//                        inversion -- an element of x that is no unit is a std::runtime_error also where no entry names
+//                        its column --, window tables over [x ; x^-1], Booth digits of the weights.  Widths and errors
+//                        as matVecSigned's.
 //   weightedSum(xs, w)   y[i] = sum_k w[k] * xs[k][i] under the encryption, ACROSS K CipherTexts of one size with one
 //                        plaintext weight per CipherText: Y[i] = prod_k X_k[i]^w[k] mod n^2 -- a federated average over K
 //                        clients' encrypted vectors.  A zero weight contributes nothing; all weights zero yield
@@ -70,6 +77,8 @@ CipherText matMulSigned(const std::vector<int64_t>& w, std::size_t rows, const C
                         bool transposed = false);
 CipherText sparseMatVec(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx, const PlainText& w,
                         const CipherText& x);
+CipherText sparseMatVecSigned(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx,
+                              const std::vector<int64_t>& w, const CipherText& x);
 CipherText weightedSum(const std::vector<CipherText>& xs, const PlainText& w);
 CipherText sum(const std::vector<CipherText>& xs);
 

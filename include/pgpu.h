@@ -659,6 +659,44 @@ int pgpu_ct_matvec_signed_plan(int key_bits, size_t rows, size_t cols, int e_bit
 int pgpu_ct_matmul_signed_plan(int key_bits, size_t n_vec, size_t rows, size_t cols, int e_bits,
                                int* window, int* slices, size_t* tile, size_t* table_bytes, size_t* products);
 
+/* Signed-weight encrypted 2-D convolution and sparse matrix-vector product on resident ciphertexts: pgpu_batch_ct_conv2d
+ * and pgpu_batch_ct_spmv for weights that may be negative (a CNN filter, a graph Laplacian),
+ *     out[n][co][oy][ox] = prod_{ci,ky,kx} x[n][ci][oy*sh + ky - ph][ox*sw + kx - pw]^w[co][ci][ky][kx] mod n^2
+ *     out[i] = prod_{ row_ptr[i] <= t < row_ptr[i+1] } x[col_idx[t]]^w[t] mod n^2,
+ * every weight a SIGNED integer in two's complement in e_bits bits exactly as for pgpu_batch_ct_matvec_signed: bit
+ * e_bits - 1 of a stored weight is its sign, bits at and above e_bits are ignored, 1 <= e_bits <= 64 * words(w), an int64
+ * array goes in as it is.  Layouts, shape rules, zero padding (a tap outside the image contributes one, whatever its
+ * weight's sign), strides, empty rows and "a column named twice contributes twice" (with weights a and -a: the ciphertext
+ * 1) are those of the unsigned calls.  The downloaded result is the canonical value, the product of Python's
+ * pow(x, w, n * n), where a negative exponent goes through pow(x, -1, n * n); it is an ordinary resident batch on the lane
+ * of x, and x is left unchanged.
+ * Schedule ("Signed-weight conv2d and spmv"): x^-1 by the batched inversion of pgpu_batch_ct_negate, ONCE per call
+ * over ALL elements of x and before the first pass (launches of kind PGPU_KERNEL_INVERT, one host round trip); then the
+ * unsigned call's launches on a window table of 2^w + 1 rows per element over [x ; x^-1] and on the radix-2^w Booth digits
+ * of the weights -- per pass of whole images for the convolution, once over every column for the sparse product -- and the
+ * unchanged folds (kinds PGPU_KERNEL_CONV / PGPU_KERNEL_SPMV).  A signed call so costs the unsigned one plus
+ * 3 * (elements of x - 1) products, where sub(conv2d(x, W+), conv2d(x, W-)) runs two of them.
+ * pgpu_batch_ct_spmv_signed inverts EVERY element of x, referenced by a column index or not: an element of x that is no
+ * unit refuses the call also where no entry of the matrix names its column.
+ * The refusals are those of the unsigned calls, decided on the host before any launch, *out untouched
+ * (PGPU_ERR_INVALID_PARAM / PGPU_ERR_UNSUPPORTED as listed at pgpu_batch_ct_conv2d and pgpu_batch_ct_spmv; the masked
+ * table-gather policy refuses both).  PGPU_ERR_NOT_INVERTIBLE: an element of x is no unit modulo n^2.  As for negate this
+ * ONE refusal FOLLOWS LAUNCHES (the inversion's forward passes; none of kind CONV / SPMV); nothing is handed out and the
+ * lane stays usable.  There is no fall-back to another route. */
+int pgpu_batch_ct_conv2d_signed(const pgpu_pubkey* key, const pgpu_batch* x, const pgpu_batch* w, const pgpu_conv2d_shape* shape,
+                                int e_bits, pgpu_batch** out);
+int pgpu_batch_ct_spmv_signed(const pgpu_pubkey* key, const pgpu_batch* x, const uint64_t* row_ptr, const uint32_t* col_idx,
+                              const pgpu_batch* w, size_t rows, int e_bits, pgpu_batch** out);
+/* What the two signed calls would run (host-side queries, need no device; every output pointer may be NULL): the arguments
+ * and fields of pgpu_ct_conv2d_plan / pgpu_ct_spmv_plan, with the window (and the tile) held against tables of 2^w + 1 rows
+ * per element, table_bytes = elements of a pass (every column of x) * (2^w + 1) * row bytes, and products = the unsigned
+ * count + 3 * (elements of x - 1) for the inversion.  PGPU_CONV_WINDOW / _TILE / _SLICES and PGPU_SPMV_WINDOW / _CHUNK force
+ * the signed calls too, read at every call.  Errors as pgpu_ct_conv2d_plan / pgpu_ct_spmv_plan. */
+int pgpu_ct_conv2d_signed_plan(int key_bits, const pgpu_conv2d_shape* shape, int e_bits, int* window, int* slices, size_t* tile,
+                               size_t* table_bytes, size_t* products);
+int pgpu_ct_spmv_signed_plan(int key_bits, size_t rows, size_t cols, size_t nnz, size_t longest_row, int e_bits,
+                             int* window, int* chunk, int* levels, size_t* table_bytes, size_t* products);
+
 /* ---- instrumentation used by bench.py (roofline) ----
  * With timing enabled every kernel launch is bracketed by two HIP events recorded on the stream
  * the kernel is launched on (no synchronisation at launch time).  pgpu_timing_collect waits for
@@ -673,11 +711,11 @@ typedef enum pgpu_kernel_kind {
   PGPU_KERNEL_SEGSUM = 6,     /* every launch of pgpu_batch_ct_segment_sum: one per level */
   PGPU_KERNEL_SEGSCAN = 7,    /* every launch of pgpu_batch_ct_segment_scan: up-sweeps (segsum_kernel) and scans */
   PGPU_KERNEL_PACK = 8,       /* the launch of pgpu_batch_ct_pack */
-  PGPU_KERNEL_SPMV = 9,       /* every launch of pgpu_batch_ct_spmv: table build, multi-exponentiation, fold levels */
+  PGPU_KERNEL_SPMV = 9,       /* every launch of pgpu_batch_ct_spmv (and of _spmv_signed but its inversion): table build, multi-exponentiation, fold levels */
   PGPU_KERNEL_WSUM = 10,      /* every launch of pgpu_batch_ct_weighted_sum: the slices' schedules, the fold */
   PGPU_KERNEL_MATMUL = 11,    /* every launch of pgpu_batch_ct_matmul: per pass the table build, the multi-exponentiation, the fold */
   PGPU_KERNEL_BUCKET = 12,    /* every launch of pgpu_batch_ct_matvec_bucket: accumulation levels, bucket reductions, Horner */
-  PGPU_KERNEL_CONV = 13,      /* every launch of pgpu_batch_ct_conv2d: per pass the table build, the multi-exponentiation, the fold */
+  PGPU_KERNEL_CONV = 13,      /* every launch of pgpu_batch_ct_conv2d (and of _conv2d_signed but its inversion): per pass the table build, the multi-exponentiation, the fold */
   PGPU_KERNEL_INVERT = 14     /* every launch of pgpu_batch_ct_negate / _sub: forward passes, walks back, the broadcast product */
 } pgpu_kernel_kind;
 int pgpu_set_timing(int enabled);

@@ -47,6 +47,8 @@ SYMBOLS = [
     "pgpu_batch_ct_negate", "pgpu_batch_ct_sub", "pgpu_ct_negate_plan",
     "pgpu_batch_ct_matvec_signed", "pgpu_ct_matvec_signed_plan",
     "pgpu_batch_ct_matmul_signed", "pgpu_ct_matmul_signed_plan",
+    "pgpu_batch_ct_conv2d_signed", "pgpu_ct_conv2d_signed_plan",
+    "pgpu_batch_ct_spmv_signed", "pgpu_ct_spmv_signed_plan",
 ]
 FEATURE_4096_SPLIT = 1
 SEGMENT_NONE = 0xFFFFFFFF      # PGPU_SEGMENT_NONE: the element is left out of that group
@@ -241,6 +243,14 @@ def lib():
     L.pgpu_ct_conv2d_plan.argtypes = [c_int, POINTER(Conv2dShape), c_int, POINTER(c_int), POINTER(c_int), POINTER(c_size_t),
                                       POINTER(c_size_t), POINTER(c_size_t)]
     L.pgpu_ct_conv2d_plan.restype = c_int
+    L.pgpu_batch_ct_conv2d_signed.argtypes = L.pgpu_batch_ct_conv2d.argtypes
+    L.pgpu_batch_ct_conv2d_signed.restype = c_int
+    L.pgpu_ct_conv2d_signed_plan.argtypes = L.pgpu_ct_conv2d_plan.argtypes
+    L.pgpu_ct_conv2d_signed_plan.restype = c_int
+    L.pgpu_batch_ct_spmv_signed.argtypes = L.pgpu_batch_ct_spmv.argtypes
+    L.pgpu_batch_ct_spmv_signed.restype = c_int
+    L.pgpu_ct_spmv_signed_plan.argtypes = L.pgpu_ct_spmv_plan.argtypes
+    L.pgpu_ct_spmv_signed_plan.restype = c_int
     _lib = L
     return L
 

@@ -50,7 +50,7 @@ def hensel_parts():
     skip = {15, 30}      # (retired in round 6: the A/B-wavefront experiment and the operand-scanning one-lane kernel)
     if not build_4096():
         skip |= {22, 23, 24}
-    return [p for p in range(78) if p not in skip]
+    return [p for p in range(84) if p not in skip]
 
 
 def _objects():
@@ -106,6 +106,10 @@ def _objects():
             hdeps_k.append(os.path.join(CSRC, "hensel_invert.hpp"))
         if part in (75, 76, 77):
             hdeps_k.append(os.path.join(CSRC, "hensel_signed.hpp"))
+        if part in (78, 79, 80):
+            hdeps_k += [os.path.join(CSRC, f) for f in ("hensel_conv_signed.hpp", "hensel_conv.hpp", "hensel_signed.hpp")]
+        if part in (81, 82, 83):
+            hdeps_k += [os.path.join(CSRC, f) for f in ("hensel_spmv_signed.hpp", "hensel_signed.hpp")]
         out.append((o, hip + [f"-DPGPU_PART={part}", "-c", src, "-o", o], [src] + hdeps_k + kdeps))
     for name in ("capi.cpp", "policy.cpp", "runtime.cpp", os.path.join("host", "bignum.cpp")):
         src = os.path.join(CSRC, name)

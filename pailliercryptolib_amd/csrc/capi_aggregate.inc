@@ -1,5 +1,5 @@
 // pailliercryptolib_amd -- the aggregation calls on resident ciphertexts (pgpu_batch_ct_matvec / _matvec_bucket / _matmul / _conv2d / _spmv / _weighted_sum /
-// _segment_sum / _segment_scan / _pack / _negate / _sub) and their plan queries (pgpu_ct_*_plan).
+// _segment_sum / _segment_scan / _pack / _negate / _sub / _matvec_signed / _matmul_signed / _conv2d_signed / _spmv_signed) and their plan queries (pgpu_ct_*_plan).
 // Part of the translation unit of capi.cpp (included there, in place, after capi_batches.inc, whose bounce buffer the plan
 // upload shares).  Every call is: its own parameter checks, the admission tail, its plan (policy.hpp), the result set-up,
 // one upload of the plan image, its launches.  What the calls have in common is written once, in the helpers below.
@@ -1385,6 +1385,242 @@ int pgpu_batch_ct_matmul_signed(const pgpu_pubkey* key, const pgpu_batch* x, con
     if (S > 1 && staged)
       HIP_TRY(hipMemcpy2DAsync(dest, n_vec * row_bytes, partial.p, t * row_bytes, t * row_bytes, rows, hipMemcpyDeviceToDevice, r.s));
   }
+  RC_TRY(lanes_order(w, r.x->lane, false));
+  return r.finish(out);
+}
+
+// ---- signed-weight convolution and sparse product (hensel_conv_signed.hpp, hensel_spmv_signed.hpp; policy.hpp:
+// conv_signed_plan, spmv_signed_*) ----
+// pgpu_batch_ct_conv2d / pgpu_batch_ct_spmv for weights in two's complement, after the signed matmul: x^-1 of ALL of x by one
+// invert_batch before the first pass (launches of kind PGPU_KERNEL_INVERT, the one refusal after launches), xinv held beside
+// x for the call, per pass the signed table over the tile's contiguous range of x and xinv, the multi-exponentiation on
+// Booth digits, the unchanged folds.  No other route exists: a missing kernel is an error.
+int pgpu_ct_conv2d_signed_plan(int key_bits, const pgpu_conv2d_shape* shape, int e_bits, int* window, int* slices, size_t* tile,
+                               size_t* table_bytes, size_t* products) {
+  if (key_bits < 1 || !shape || e_bits < 1)
+    return fail(PGPU_ERR_INVALID_PARAM, "signed conv2d plan: key_bits and e_bits must be positive, the shape not null");
+  policy::ConvDims g{};
+  if (!conv_dims(shape, &g)) return fail(PGPU_ERR_INVALID_PARAM, std::string("signed conv2d plan") + kConvShapeMsg);
+  int G = 0, K = 0;
+  if (!policy::matvec_geometry(key_bits, &G, &K) || !pgpu::conv_signed_has(G, K))
+    return fail(PGPU_ERR_UNSUPPORTED, "signed conv2d: keys of this size have no pair rows (1024- to 3072-bit key classes only)");
+  const size_t row_bytes = (size_t)2 * G * K * sizeof(uint32_t);
+  policy::ConvPlan plan;
+  policy::conv_signed_plan(G, shape->n_img, g.elems, g.n_o, g.taps, e_bits, row_bytes, &plan);
+  if (plan.products >= 18446744073709551615.0) return fail(PGPU_ERR_INVALID_PARAM, "signed conv2d plan: the product count overflows");
+  if (window) *window = plan.window;
+  if (slices) *slices = (int)plan.slices;
+  if (tile) *tile = plan.tile;
+  if (table_bytes) *table_bytes = plan.tile * g.elems * (((size_t)1 << plan.window) + 1) * row_bytes;
+  if (products) *products = (size_t)plan.products;
+  return PGPU_OK;
+}
+
+int pgpu_batch_ct_conv2d_signed(const pgpu_pubkey* key, const pgpu_batch* x, const pgpu_batch* w, const pgpu_conv2d_shape* shape,
+                                int e_bits, pgpu_batch** out) {
+  RC_TRY(rt::check_ready());
+  if (!key || !x || !w || !shape || !out) return fail(PGPU_ERR_INVALID_PARAM, "null argument");
+  RC_TRY(check_gen(key->gen, "key"));
+  RC_TRY(check_gen(x->gen, "batch"));
+  RC_TRY(check_gen(w->gen, "batch"));
+  policy::ConvDims g{};
+  if (!conv_dims(shape, &g)) return fail(PGPU_ERR_INVALID_PARAM, std::string("signed conv2d error") + kConvShapeMsg);
+  if (x->count != g.x_count) return fail(PGPU_ERR_INVALID_PARAM, "signed conv2d error: Size mismatch! (x must hold n_img * c_in * h * w ciphertexts)");
+  if (x->words != 2 * key->n_words) return fail(PGPU_ERR_INVALID_PARAM, "signed conv2d error: ciphertext width mismatch");
+  if (w->mont || w->pair_l2) return fail(PGPU_ERR_INVALID_PARAM, "signed conv2d error: the filters must be a plain uploaded batch");
+  if (w->count != g.w_count) return fail(PGPU_ERR_INVALID_PARAM, "signed conv2d error: Size mismatch! (the filters must hold c_out * c_in * kh * kw values)");
+  if (e_bits < 1 || e_bits > 64 * w->words) return fail(PGPU_ERR_INVALID_PARAM, "signed conv2d error: e_bits outside the rows of the filter batch");
+  static const AggOp op{"signed conv2d", "images", " and this call indexes its window tables by digits of the plaintext filters and by positions "
+                                                   "derived from the shape; no masked variant exists",
+                        pgpu::conv_signed_has, "ciphertext batch belongs to a different key"};
+  const pgpu_pubkey::PubForm* pf = nullptr;
+  RC_TRY(agg_admit(op, key, &x, 1, &pf));
+  const int G = pf->H, K = pf->K;
+  const size_t LQ = (size_t)2 * G * K, row_bytes = LQ * sizeof(uint32_t);
+  policy::ConvPlan plan;
+  policy::conv_signed_plan(G, shape->n_img, g.elems, g.n_o, g.taps, e_bits, row_bytes, &plan);
+  const int win = plan.window;
+  const size_t trows = ((size_t)1 << win) + 1;
+  const size_t S_max = std::max(plan.slices, plan.last_slices);
+  // x as pair rows, then the inverses of all n_img * elems elements, once, before the first pass: nothing of this call's own
+  // has been launched when the inversion refuses
+  std::unique_ptr<pgpu_batch> tx, xinv;
+  const pgpu_batch* xp = nullptr;
+  RC_TRY(as_pair_batch(key, x, &xp, &tx));
+  RC_TRY(invert_batch(key, pf, "signed conv2d", xp, nullptr, xp->lane, &xinv));
+  AggRun r;
+  RC_TRY(r.open(key, pf, xp, g.out_count));
+  RC_TRY(lanes_order(w, r.x->lane, true));
+  // the blocks of pgpu_batch_ct_conv2d, the table one row longer per element
+  rt::DevMem table, partial;
+  RC_TRY(table.alloc(*r.dev, r.s, plan.tile * g.elems * trows * row_bytes));
+  if (S_max > 1) RC_TRY(partial.alloc(*r.dev, r.s, S_max * plan.tile * g.n_o * row_bytes));
+  for (size_t p = 0; p < plan.passes; ++p) {
+    const size_t i0 = p * plan.tile, t = p + 1 == plan.passes ? plan.last : plan.tile, n_out = t * g.n_o;
+    const size_t S = p + 1 == plan.passes ? plan.last_slices : plan.slices;
+    uint32_t* dest = r.o->prow(0) + i0 * g.n_o * LQ;
+    {
+      // the unchanged signed table build over the tile's range of x and xinv
+      pgpu::SignedTableArgs ta{};
+      ta.ctx = hensel_pub_view(pf, r.dev->index);
+      ta.x = r.x->prow(0) + i0 * g.elems * LQ;
+      ta.xinv = xinv->prow(0) + i0 * g.elems * LQ;
+      ta.table = (uint32_t*)table.p;
+      ta.window = win;
+      ta.elems = t * g.elems;
+      RC_TRY(timed_launch(r, 2 * t * g.elems, G, PGPU_KERNEL_CONV, "signed conv2d", [&](unsigned blocks) { return pgpu::launch_matvec_signed_table(G, K, ta, blocks, r.s); }));
+    }
+    pgpu::ConvArgs a{};
+    a.ctx = hensel_pub_view(pf, r.dev->index);
+    a.table = (const uint32_t*)table.p;
+    a.wt = w->ptr(0);
+    a.w_stride = (size_t)w->words;
+    a.w_words = w->words;
+    a.e_bits = e_bits;
+    a.window = win;
+    a.slices = (int)S;
+    a.n_out = n_out;
+    a.c_in = (uint32_t)shape->c_in;       // (conv_geometry: every one of these below 2^31)
+    a.h = (uint32_t)shape->h;
+    a.w = (uint32_t)shape->w;
+    a.c_out = (uint32_t)shape->c_out;
+    a.kh = (uint32_t)shape->kh;
+    a.kw = (uint32_t)shape->kw;
+    a.sh = (uint32_t)std::min(shape->stride_h, shape->h + 2 * shape->pad_h);
+    a.sw = (uint32_t)std::min(shape->stride_w, shape->w + 2 * shape->pad_w);
+    a.ph = (uint32_t)shape->pad_h;
+    a.pw = (uint32_t)shape->pad_w;
+    a.oh = (uint32_t)g.oh;
+    a.ow = (uint32_t)g.ow;
+    a.out = S > 1 ? (uint32_t*)partial.p : dest;
+    a.o_slice_stride = S > 1 ? n_out : 0;
+    RC_TRY(timed_launch(r, n_out, G, PGPU_KERNEL_CONV, "signed conv2d", [&](unsigned blocks) { return pgpu::launch_conv_signed(G, K, a, blocks, r.s); }, S));
+    // the fold of pgpu_batch_ct_conv2d
+    for (size_t cur = S; cur > 1;) {
+      const size_t h = (cur + 1) / 2;
+      pgpu::PairOpsArgs pa{};
+      pa.count = (cur - h) * n_out;
+      const pgpu_pubkey::PubForm* lf = pair_op_form(key, pf, pa.count);
+      pa.ctx = hensel_pub_view(lf, r.dev->index);
+      pa.op = pgpu::PO_MUL;
+      pa.a = (const uint32_t*)partial.p;
+      pa.b = (const uint32_t*)partial.p + h * n_out * LQ;
+      pa.b_stride = LQ;
+      pa.out = h == 1 ? dest : (uint32_t*)partial.p;
+      RC_TRY(pair_op_launch(*r.dev, lf, pa, r.s, PGPU_KERNEL_CONV));
+      cur = h;
+    }
+  }
+  RC_TRY(lanes_order(w, r.x->lane, false));
+  return r.finish(out);
+}
+
+int pgpu_ct_spmv_signed_plan(int key_bits, size_t rows, size_t cols, size_t nnz, size_t longest_row, int e_bits,
+                             int* window, int* chunk, int* levels, size_t* table_bytes, size_t* products) {
+  constexpr size_t kMax = (size_t)1 << 31;
+  if (key_bits < 1 || rows == 0 || cols == 0 || nnz == 0 || e_bits < 1 || longest_row == 0 || longest_row > nnz ||
+      rows >= kMax || nnz >= kMax || (nnz + longest_row - 1) / longest_row > rows)
+    return fail(PGPU_ERR_INVALID_PARAM, "signed spmv plan: key_bits, rows, cols, nnz and e_bits must be positive, rows and nnz below 2^31, "
+                                        "longest_row between ceil(nnz / rows) and nnz");
+  int G = 0, K = 0;
+  if (!policy::matvec_geometry(key_bits, &G, &K) || !pgpu::spmv_signed_has(G, K))
+    return fail(PGPU_ERR_UNSUPPORTED, "signed spmv: keys of this size have no pair rows (1024- to 3072-bit key classes only)");
+  const size_t row_bytes = (size_t)2 * G * K * sizeof(uint32_t);
+  const int c = policy::spmv_chunk(G, nnz, rows);
+  const size_t chains = policy::spmv_chains_estimate(rows, nnz, longest_row, c);
+  const int w = policy::spmv_signed_window(rows, cols, nnz, chains, e_bits, row_bytes);
+  if (window) *window = w;
+  if (chunk) *chunk = c;
+  if (levels) *levels = policy::spmv_levels(c, longest_row);
+  if (table_bytes) *table_bytes = cols * (((size_t)1 << w) + 1) * row_bytes;
+  if (products) *products = (size_t)policy::spmv_signed_products(rows, cols, nnz, chains, e_bits, w);
+  return PGPU_OK;
+}
+
+int pgpu_batch_ct_spmv_signed(const pgpu_pubkey* key, const pgpu_batch* x, const uint64_t* row_ptr, const uint32_t* col_idx,
+                              const pgpu_batch* w, size_t rows, int e_bits, pgpu_batch** out) {
+  RC_TRY(rt::check_ready());
+  if (!key || !x || !row_ptr || !col_idx || !w || !out) return fail(PGPU_ERR_INVALID_PARAM, "null argument");
+  RC_TRY(check_gen(key->gen, "key"));
+  RC_TRY(check_gen(x->gen, "batch"));
+  RC_TRY(check_gen(w->gen, "batch"));
+  const size_t cols = x->count;
+  // (CSR positions, rows and chains are 31-bit fields of a descriptor)
+  constexpr size_t kMax = (size_t)1 << 31;
+  if (rows == 0 || rows >= kMax) return fail(PGPU_ERR_INVALID_PARAM, "signed spmv error: rows must be positive and below 2^31");
+  if (x->words != 2 * key->n_words) return fail(PGPU_ERR_INVALID_PARAM, "signed spmv error: ciphertext width mismatch");
+  if (w->mont || w->pair_l2) return fail(PGPU_ERR_INVALID_PARAM, "signed spmv error: the weights must be a plain uploaded batch");
+  if (row_ptr[0] != 0) return fail(PGPU_ERR_INVALID_PARAM, "signed spmv error: row_ptr[0] must be 0");
+  for (size_t i = 0; i < rows; ++i)
+    if (row_ptr[i + 1] < row_ptr[i]) return fail(PGPU_ERR_INVALID_PARAM, "signed spmv error: row_ptr must be non-decreasing");
+  if (row_ptr[rows] == 0) return fail(PGPU_ERR_INVALID_PARAM, "signed spmv error: the matrix has no entries (nnz == 0)");
+  if (row_ptr[rows] >= kMax) return fail(PGPU_ERR_INVALID_PARAM, "signed spmv error: nnz must stay below 2^31");
+  const size_t nnz = (size_t)row_ptr[rows];
+  if (w->count != nnz) return fail(PGPU_ERR_INVALID_PARAM, "signed spmv error: Size mismatch! (the weights must hold row_ptr[rows] values)");
+  for (size_t t = 0; t < nnz; ++t)
+    if (col_idx[t] >= cols) return fail(PGPU_ERR_INVALID_PARAM, "signed spmv error: a column index is not below count(x)");
+  if (e_bits < 1 || e_bits > 64 * w->words) return fail(PGPU_ERR_INVALID_PARAM, "signed spmv error: e_bits outside the rows of the weight batch");
+  static const AggOp op{"signed spmv", "rows", " and this call indexes its window tables by the plaintext column numbers and by digits of the "
+                                               "plaintext weights; no masked variant exists",
+                        pgpu::spmv_signed_has, nullptr};
+  const pgpu_pubkey::PubForm* pf = nullptr;
+  RC_TRY(agg_admit(op, key, &x, 1, &pf));
+  // the plan of pgpu_batch_ct_spmv, on the host; the window held against the signed table
+  const int G = pf->H, K = pf->K;
+  const size_t LQ = (size_t)2 * G * K, row_bytes = LQ * sizeof(uint32_t);
+  policy::SpmvPlan plan;
+  if (!policy::spmv_plan(row_ptr, rows, policy::spmv_chunk(G, nnz, rows), &plan))
+    return fail(PGPU_ERR_INVALID_PARAM, "signed spmv error: more chains than a 32-bit descriptor addresses");
+  const int win = policy::spmv_signed_window(rows, cols, nnz, plan.n_chains, e_bits, row_bytes);
+  const size_t trows = ((size_t)1 << win) + 1;
+  policy::SpmvImage img;
+  policy::spmv_image(col_idx, nnz, plan, &img);
+  // x as pair rows, then the inverses of ALL of its elements, referenced by a column index or not: nothing of this call's
+  // own has been launched when the inversion refuses
+  std::unique_ptr<pgpu_batch> tx, xinv;
+  const pgpu_batch* xp = nullptr;
+  RC_TRY(as_pair_batch(key, x, &xp, &tx));
+  RC_TRY(invert_batch(key, pf, "signed spmv", xp, nullptr, xp->lane, &xinv));
+  AggRun r;
+  RC_TRY(r.open(key, pf, xp, rows));
+  RC_TRY(lanes_order(w, r.x->lane, true));
+  rt::DevMem table, dimage, partial;
+  RC_TRY(table.alloc(*r.dev, r.s, cols * trows * row_bytes));
+  if (img.region[0]) RC_TRY(partial.alloc(*r.dev, r.s, (img.region[0] + img.region[1]) * row_bytes));
+  RC_TRY(upload_plan_image(*r.dev, r.s, img.image.data(), img.image.size(), &dimage));
+  {
+    // the unchanged signed table build over every column of x and xinv
+    pgpu::SignedTableArgs ta{};
+    ta.ctx = hensel_pub_view(pf, r.dev->index);
+    ta.x = r.x->prow(0);
+    ta.xinv = xinv->prow(0);
+    ta.table = (uint32_t*)table.p;
+    ta.window = win;
+    ta.elems = cols;
+    RC_TRY(timed_launch(r, 2 * cols, G, PGPU_KERNEL_SPMV, "signed spmv", [&](unsigned blocks) { return pgpu::launch_matvec_signed_table(G, K, ta, blocks, r.s); }));
+  }
+  uint32_t* const reg[2] = {(uint32_t*)partial.p, partial.p ? (uint32_t*)partial.p + img.region[0] * LQ : nullptr};
+  {
+    pgpu::SpmvArgs a{};
+    a.ctx = hensel_pub_view(pf, r.dev->index);
+    a.table = (const uint32_t*)table.p;
+    a.col_idx = (const uint32_t*)dimage.p;
+    a.w = w->ptr(0);
+    a.w_stride = (size_t)w->words;
+    a.w_words = w->words;
+    a.e_bits = e_bits;
+    a.window = win;
+    a.chunks = (const pgpu::SegsumChunk*)((const char*)dimage.p + img.chains_at);
+    a.n_chunks = plan.chains.size();
+    a.out = r.o->prow(0);
+    a.partial = reg[0];
+    RC_TRY(timed_launch(r, a.n_chunks, G, PGPU_KERNEL_SPMV, "signed spmv", [&](unsigned blocks) { return pgpu::launch_spmv_signed(G, K, a, blocks, r.s); }));
+  }
+  // the fold levels of pgpu_batch_ct_spmv
+  const pgpu_pubkey::PubForm* wide = wide_form(key, pf, pgpu::segsum_wide_has);
+  for (size_t f = 0; f < plan.fold.levels.size(); ++f)
+    RC_TRY(segsum_level(r, wide, reg[f & 1], nullptr, (const char*)dimage.p + img.fold_at[f], plan.fold.levels[f].chunks.size(),
+                        r.o->prow(0), reg[(f + 1) & 1], PGPU_KERNEL_SPMV));
   RC_TRY(lanes_order(w, r.x->lane, false));
   return r.finish(out);
 }

@@ -20,6 +20,21 @@ void ensure_context();
 
 inline int words_for_bits(int bits) { return bits <= 0 ? 1 : (bits + 63) / 64; }
 
+// signed weights as the one-word two's-complement rows the signed calls read; returns the smallest two's-complement width
+// that holds every weight: the bits of v (v >= 0) or of ~v (v < 0), and the sign
+inline int signed_weight_words(const std::vector<int64_t>& w, std::vector<uint64_t>* words) {
+  int ebits = 1;
+  words->resize(w.size());
+  for (std::size_t k = 0; k < w.size(); ++k) {
+    uint64_t m = (uint64_t)(w[k] < 0 ? ~w[k] : w[k]);
+    int b = 1;
+    for (; m; m >>= 1) ++b;
+    if (b > ebits) ebits = b;
+    (*words)[k] = (uint64_t)w[k];
+  }
+  return ebits;
+}
+
 // ---- host threads of the per-element loops (reference ipcl/include/ipcl/utils/util.hpp:77-113:
 // OMPUtilities::MaxThreads / assignOMPThreads; loops at mod_exp.cpp:607-612, pri_key.cpp:122-145,
 // ciphertext.cpp:53-68).  The reference opens an OpenMP region per loop; here a small persistent team of worker

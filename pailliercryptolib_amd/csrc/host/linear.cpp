@@ -1,5 +1,5 @@
-// ipcl::ext::matVec / dot / matVecBucket / matMul / matVecSigned / dotSigned / matMulSigned / sparseMatVec / weightedSum / sum -- linear maps on encrypted vectors (include/ipcl/ext/linear.hpp): one
-// pgpu_batch_ct_matvec / pgpu_batch_ct_matvec_bucket / pgpu_batch_ct_matmul / pgpu_batch_ct_matvec_signed / pgpu_batch_ct_matmul_signed / pgpu_batch_ct_spmv / pgpu_batch_ct_weighted_sum call on resident batches.  The reference composes such a map from CipherText::operator*
+// ipcl::ext::matVec / dot / matVecBucket / matMul / matVecSigned / dotSigned / matMulSigned / sparseMatVec / sparseMatVecSigned / weightedSum / sum -- linear maps on encrypted vectors (include/ipcl/ext/linear.hpp): one
+// pgpu_batch_ct_matvec / pgpu_batch_ct_matvec_bucket / pgpu_batch_ct_matmul / pgpu_batch_ct_matvec_signed / pgpu_batch_ct_matmul_signed / pgpu_batch_ct_spmv / pgpu_batch_ct_spmv_signed / pgpu_batch_ct_weighted_sum call on resident batches.  The reference composes such a map from CipherText::operator*
 // (ciphertext.cpp:83-106) and operator+ (ciphertext.cpp:35-72) term by term.
 #include "ipcl/ext/linear.hpp"
 
@@ -79,16 +79,8 @@ CipherText CipherText::signedLinearMap(const std::vector<int64_t>& w, std::size_
               batch ? "matMulSigned error: Size mismatch!" : "matVecSigned error: Size mismatch!");
   const BigNumber& nsq = *(m_pk->getNSQ());
   const int W = detail::words_for_bits(nsq.BitSize());
-  // the smallest two's-complement width that holds every weight: the bits of v (v >= 0) or of ~v (v < 0), and the sign
-  int ebits = 1;
-  std::vector<uint64_t> words(w.size());
-  for (std::size_t k = 0; k < w.size(); ++k) {
-    uint64_t m = (uint64_t)(w[k] < 0 ? ~w[k] : w[k]);
-    int b = 1;
-    for (; m; m >>= 1) ++b;
-    ebits = std::max(ebits, b);
-    words[k] = (uint64_t)w[k];
-  }
+  std::vector<uint64_t> words;
+  const int ebits = detail::signed_weight_words(w, &words);
   auto dx = deviceBatch(W, &nsq), dw = detail::DeviceBatch::upload(words, words.size(), 1);
   pgpu_batch* o = nullptr;
   if (batch)
@@ -116,6 +108,23 @@ CipherText CipherText::sparseLinearMap(const std::vector<uint64_t>& row_ptr, con
   IPCL_GPU_CHECK(pgpu_batch_ct_spmv(m_pk->device()->h, dx->h, row_ptr.data(), col_idx.data(), dw->h, row_ptr.size() - 1,
                                     ebits, &o),
                  "sparseMatVec");
+  return CipherText(m_pk, detail::DeviceBatch::adopt(o));
+}
+
+CipherText CipherText::signedSparseLinearMap(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx,
+                                             const std::vector<int64_t>& w) const {
+  ERROR_CHECK(m_size > 0, "sparseMatVecSigned error: empty CipherText");
+  ERROR_CHECK(row_ptr.size() >= 2 && !w.empty(), "sparseMatVecSigned error: empty matrix");
+  ERROR_CHECK(row_ptr.back() == col_idx.size() && w.size() == col_idx.size(), "sparseMatVecSigned error: Size mismatch!");
+  const BigNumber& nsq = *(m_pk->getNSQ());
+  const int W = detail::words_for_bits(nsq.BitSize());
+  std::vector<uint64_t> words;
+  const int ebits = detail::signed_weight_words(w, &words);
+  auto dx = deviceBatch(W, &nsq), dw = detail::DeviceBatch::upload(words, words.size(), 1);
+  pgpu_batch* o = nullptr;
+  IPCL_GPU_CHECK(pgpu_batch_ct_spmv_signed(m_pk->device()->h, dx->h, row_ptr.data(), col_idx.data(), dw->h, row_ptr.size() - 1,
+                                           ebits, &o),
+                 "sparseMatVecSigned");
   return CipherText(m_pk, detail::DeviceBatch::adopt(o));
 }
 
@@ -182,6 +191,10 @@ CipherText matMulSigned(const std::vector<int64_t>& w, std::size_t rows, const C
 CipherText sparseMatVec(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx, const PlainText& w,
                         const CipherText& x) {
   return x.sparseLinearMap(row_ptr, col_idx, w);
+}
+CipherText sparseMatVecSigned(const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx,
+                              const std::vector<int64_t>& w, const CipherText& x) {
+  return x.signedSparseLinearMap(row_ptr, col_idx, w);
 }
 
 }  // namespace ext

@@ -1,5 +1,5 @@
 // pailliercryptolib_amd -- instantiations of the split-form CRT-decrypt exponentiation (hensel.hpp), split over
-// PGPU_PART = 0..77 so that they compile in parallel (75-77: the signed-weight matrix-vector and matrix products; 70-73: the walk back of the batched inversion, 74: its forward pass in the (8,9) form; 67-69: the encrypted 2-D convolution; 63-66: the bucket reduction of the bucket-method matvec; 60-62: the encrypted matrix product; 56-59: the encrypted weighted sum of K resident batches; 53-55: the encrypted sparse matrix-vector product; 38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 45-47: the encrypted segmented prefix sum; 48-51: the encrypted slot packing; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
+// PGPU_PART = 0..83 so that they compile in parallel (78-80: the signed-weight 2-D convolution, 81-83: the signed-weight sparse matrix-vector product; 75-77:the signed-weight matrix-vector and matrix products; 70-73: the walk back of the batched inversion, 74: its forward pass in the (8,9) form; 67-69: the encrypted 2-D convolution; 63-66: the bucket reduction of the bucket-method matvec; 60-62: the encrypted matrix product; 56-59: the encrypted weighted sum of K resident batches; 53-55: the encrypted sparse matrix-vector product; 38-40: the encrypted matrix-vector product; 41-44: the encrypted segmented sum; 45-47: the encrypted segmented prefix sum; 48-51: the encrypted slot packing; 3, 4, 10: the fixed-base DJN encrypt; 5, 6, 8, 9: the generic modexp; 7:
 // the two-wavefronts-per-SIMD build of the (2,19) decrypt form; 11-13: element-wise operations on pair rows).
 #include "hensel_seq.hpp"
 #include "launch.hpp"
@@ -48,9 +48,15 @@
 #if defined(PGPU_PART) && PGPU_PART >= 75 && PGPU_PART <= 77
 #include "hensel_signed.hpp"    // the signed-weight matvec / matmul: a table over [x ; x^-1], Booth digits of the weights
 #endif
+#if defined(PGPU_PART) && PGPU_PART >= 78 && PGPU_PART <= 80
+#include "hensel_conv_signed.hpp"   // the signed-weight convolution: conv_kernel's schedule on the signed table and Booth digits
+#endif
+#if defined(PGPU_PART) && PGPU_PART >= 81 && PGPU_PART <= 83
+#include "hensel_spmv_signed.hpp"   // the signed-weight sparse product: spmv_kernel's schedule on the signed table and Booth digits
+#endif
 
 #ifndef PGPU_PART
-#error "compile with -DPGPU_PART=0..77 (15 and 30 are retired)"
+#error "compile with -DPGPU_PART=0..83 (15 and 30 are retired)"
 #endif
 
 namespace pgpu {
@@ -743,6 +749,46 @@ bool PGPU_SG_NAME(launch_matvec_signed)(int G, int K, const MatvecArgs& a, unsig
 bool PGPU_SG_NAME(launch_matmul_signed)(int G, int K, const MatmulArgs& a, unsigned blocks, hipStream_t s) {
   if (G != PGPU_SG_G || K != PGPU_SG_K) return false;
   hipLaunchKernelGGL((matmul_signed_kernel<PGPU_SG_G, PGPU_SG_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
+  return true;
+}
+#elif PGPU_PART >= 78 && PGPU_PART <= 80
+// the signed-weight 2-D convolution (hensel_conv_signed.hpp): one geometry per part
+#if PGPU_PART == 78
+#define PGPU_CS_G 2
+#define PGPU_CS_K 19
+#define PGPU_CS_NAME launch_conv_signed_part78
+#elif PGPU_PART == 79
+#define PGPU_CS_G 4
+#define PGPU_CS_K 18
+#define PGPU_CS_NAME launch_conv_signed_part79
+#else
+#define PGPU_CS_G 8
+#define PGPU_CS_K 14
+#define PGPU_CS_NAME launch_conv_signed_part80
+#endif
+bool PGPU_CS_NAME(int G, int K, const ConvArgs& a, unsigned blocks, hipStream_t s) {
+  if (G != PGPU_CS_G || K != PGPU_CS_K) return false;
+  hipLaunchKernelGGL((conv_signed_kernel<PGPU_CS_G, PGPU_CS_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
+  return true;
+}
+#elif PGPU_PART >= 81 && PGPU_PART <= 83
+// the signed-weight sparse matrix-vector product (hensel_spmv_signed.hpp): one geometry per part
+#if PGPU_PART == 81
+#define PGPU_SPS_G 2
+#define PGPU_SPS_K 19
+#define PGPU_SPS_NAME launch_spmv_signed_part81
+#elif PGPU_PART == 82
+#define PGPU_SPS_G 4
+#define PGPU_SPS_K 18
+#define PGPU_SPS_NAME launch_spmv_signed_part82
+#else
+#define PGPU_SPS_G 8
+#define PGPU_SPS_K 14
+#define PGPU_SPS_NAME launch_spmv_signed_part83
+#endif
+bool PGPU_SPS_NAME(int G, int K, const SpmvArgs& a, unsigned blocks, hipStream_t s) {
+  if (G != PGPU_SPS_G || K != PGPU_SPS_K) return false;
+  hipLaunchKernelGGL((spmv_signed_kernel<PGPU_SPS_G, PGPU_SPS_K>), dim3(blocks), dim3(kWGThreads), 0, s, a);
   return true;
 }
 #else

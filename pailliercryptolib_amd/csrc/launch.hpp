@@ -458,6 +458,27 @@ inline bool launch_conv(int G, int K, const ConvArgs& a, unsigned blocks, hipStr
          launch_conv_part69(G, K, a, blocks, s);
 }
 
+// The signed-weight 2-D convolution and sparse matrix-vector product (hensel_conv_signed.hpp, hensel_spmv_signed.hpp;
+// k_hensel.hip parts 78-80 and 81-83): conv_kernel's and spmv_kernel's schedules over the tables of
+// launch_matvec_signed_table, on Booth digits of the weights, in the geometries matvec_has lists (the inversion runs through
+// launch_segscan / launch_invert, the folds through the element-wise pair products and launch_segsum)
+inline bool conv_signed_has(int G, int K) { return conv_has(G, K) && matvec_signed_has(G, K); }
+inline bool spmv_signed_has(int G, int K) { return spmv_has(G, K) && matvec_signed_has(G, K); }
+bool launch_conv_signed_part78(int G, int K, const ConvArgs& a, unsigned blocks, hipStream_t s);
+bool launch_conv_signed_part79(int G, int K, const ConvArgs& a, unsigned blocks, hipStream_t s);
+bool launch_conv_signed_part80(int G, int K, const ConvArgs& a, unsigned blocks, hipStream_t s);
+inline bool launch_conv_signed(int G, int K, const ConvArgs& a, unsigned blocks, hipStream_t s) {
+  return launch_conv_signed_part78(G, K, a, blocks, s) || launch_conv_signed_part79(G, K, a, blocks, s) ||
+         launch_conv_signed_part80(G, K, a, blocks, s);
+}
+bool launch_spmv_signed_part81(int G, int K, const SpmvArgs& a, unsigned blocks, hipStream_t s);
+bool launch_spmv_signed_part82(int G, int K, const SpmvArgs& a, unsigned blocks, hipStream_t s);
+bool launch_spmv_signed_part83(int G, int K, const SpmvArgs& a, unsigned blocks, hipStream_t s);
+inline bool launch_spmv_signed(int G, int K, const SpmvArgs& a, unsigned blocks, hipStream_t s) {
+  return launch_spmv_signed_part81(G, K, a, blocks, s) || launch_spmv_signed_part82(G, K, a, blocks, s) ||
+         launch_spmv_signed_part83(G, K, a, blocks, s);
+}
+
 // DJN encrypt to pair rows in the same form (k_hensel.hip parts 20, 21, 28): (4,18) 2048-bit keys, (8,14) 3072, (2,19) 1024
 inline bool hensel_fb_encrypt_seq_has(int G, int K) { return (G == 4 && K == 18) || (G == 8 && K == 14) || (G == 2 && K == 19); }
 bool launch_hensel_fb_encrypt_seq_part28(int G, int K, const HenselFbArgs& a, unsigned blocks, hipStream_t s);

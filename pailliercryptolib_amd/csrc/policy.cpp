@@ -338,8 +338,9 @@ static double tiled_products_with(long forced_s, int G, size_t n, size_t elems, 
   const size_t full = n / tile, rem = n % tile;
   return (double)full * pass(tile) + (rem ? pass(rem) : 0.0);
 }
+// (extra_rows: rows of an element's table beyond 2^w -- 0, or 1 for the signed calls' tables over [x ; x^-1]; only the cap sees them)
 static void tiled_plan_with(long fw, long ft, long fs, int G, size_t n, size_t elems, size_t rows, size_t cols, int e_bits,
-                            size_t row_bytes, MatmulPlan* plan) {
+                            size_t row_bytes, size_t extra_rows, MatmulPlan* plan) {
   const int w_lo = fw > 0 ? (int)std::min(fw, 6L) : 1, w_hi = fw > 0 ? w_lo : 6;
   int best_w = w_lo;
   size_t best_t = ft > 0 ? std::min((size_t)ft, n) : 1;
@@ -347,7 +348,7 @@ static void tiled_plan_with(long fw, long ft, long fs, int G, size_t n, size_t e
   for (int w = w_lo; w <= w_hi; ++w) {
     // items whose tables fit the cap at this window; a forced value is taken as it is
     size_t t_hi = 0;
-    if (elems <= kMatvecTableCap) t_hi = std::min(n, kMatvecTableCap / (elems * ((size_t)1 << w) * row_bytes));
+    if (elems <= kMatvecTableCap) t_hi = std::min(n, kMatvecTableCap / (elems * (((size_t)1 << w) + extra_rows) * row_bytes));
     if (t_hi == 0) {
       if (w > w_lo) break;
       t_hi = 1;     // one oversized item: tile = 1 at the smallest window
@@ -381,7 +382,7 @@ double matmul_products(int G, size_t n_vec, size_t rows, size_t cols, int e_bits
 }
 void matmul_plan(int G, size_t n_vec, size_t rows, size_t cols, int e_bits, size_t row_bytes, MatmulPlan* plan) {
   tiled_plan_with(env_now("PGPU_MATMUL_WINDOW"), env_now("PGPU_MATMUL_TILE"), env_now("PGPU_MATMUL_SLICES"), G, n_vec, cols, rows,
-                  cols, e_bits, row_bytes, plan);
+                  cols, e_bits, row_bytes, 0, plan);
 }
 
 
@@ -404,38 +405,11 @@ int matvec_signed_window(size_t rows, size_t cols, int e_bits, size_t slices, si
   return best;
 }
 void matmul_signed_plan(int G, size_t n_vec, size_t rows, size_t cols, int e_bits, size_t row_bytes, MatmulPlan* plan) {
-  const long fw = env_now("PGPU_MATMUL_WINDOW"), ft = env_now("PGPU_MATMUL_TILE"), fs = env_now("PGPU_MATMUL_SLICES");
   // tiled_plan_with over tables of 2^w + 1 rows per element
-  const int w_lo = fw > 0 ? (int)std::min(fw, 6L) : 1, w_hi = fw > 0 ? w_lo : 6;
-  int best_w = w_lo;
-  size_t best_t = ft > 0 ? std::min((size_t)ft, n_vec) : 1;
-  double best_cost = -1;
-  for (int w = w_lo; w <= w_hi; ++w) {
-    size_t t_hi = 0;
-    if (cols <= kMatvecTableCap) t_hi = std::min(n_vec, kMatvecTableCap / (cols * (((size_t)1 << w) + 1) * row_bytes));
-    if (t_hi == 0) {
-      if (w > w_lo) break;
-      t_hi = 1;     // one oversized vector: tile = 1 at the smallest window
-    }
-    size_t t_lo = 1;
-    if (ft > 0) t_lo = t_hi = std::min((size_t)ft, n_vec);
-    for (size_t t = t_hi; t >= t_lo; --t) {
-      const double cost = tiled_products_with(fs, G, n_vec, cols, rows, cols, e_bits, w, t);
-      if (best_cost < 0 || cost < best_cost || (cost == best_cost && (t > best_t || (t == best_t && w < best_w)))) {
-        best_cost = cost;
-        best_w = w;
-        best_t = t;
-      }
-    }
-  }
-  plan->window = best_w;
-  plan->tile = best_t;
-  plan->passes = (n_vec + best_t - 1) / best_t;
-  plan->last = n_vec - (plan->passes - 1) * best_t;
-  plan->slices = tiled_slices_with(fs, G, best_t, rows, cols);
-  plan->last_slices = tiled_slices_with(fs, G, plan->last, rows, cols);
+  tiled_plan_with(env_now("PGPU_MATMUL_WINDOW"), env_now("PGPU_MATMUL_TILE"), env_now("PGPU_MATMUL_SLICES"), G, n_vec, cols, rows,
+                  cols, e_bits, row_bytes, 1, plan);
   // the one inversion runs over all n_vec * cols elements before the first pass
-  plan->products = best_cost + (double)invert_products(n_vec * cols);
+  plan->products += (double)invert_products(n_vec * cols);
 }
 
 
@@ -451,7 +425,13 @@ double conv_products(int G, size_t n_img, size_t elems, size_t n_o, size_t taps,
 }
 void conv_plan(int G, size_t n_img, size_t elems, size_t n_o, size_t taps, int e_bits, size_t row_bytes, ConvPlan* plan) {
   tiled_plan_with(env_now("PGPU_CONV_WINDOW"), env_now("PGPU_CONV_TILE"), env_now("PGPU_CONV_SLICES"), G, n_img, elems, n_o,
-                  taps, e_bits, row_bytes, plan);
+                  taps, e_bits, row_bytes, 0, plan);
+}
+// the signed call: conv_plan over tables of 2^w + 1 rows per element, plus the one inversion of all n_img * elems elements
+void conv_signed_plan(int G, size_t n_img, size_t elems, size_t n_o, size_t taps, int e_bits, size_t row_bytes, ConvPlan* plan) {
+  tiled_plan_with(env_now("PGPU_CONV_WINDOW"), env_now("PGPU_CONV_TILE"), env_now("PGPU_CONV_SLICES"), G, n_img, elems, n_o,
+                  taps, e_bits, row_bytes, 1, plan);
+  plan->products += (double)invert_products(n_img * elems);
 }
 bool conv_geometry(const size_t d[11], ConvDims* g) {
   const size_t n_img = d[0], c_in = d[1], h = d[2], w = d[3], c_out = d[4], kh = d[5], kw = d[6], sh = d[7], sw = d[8], ph = d[9], pw = d[10];
@@ -718,17 +698,29 @@ double spmv_products(size_t rows, size_t cols, size_t nnz, size_t chains, int e_
   return (double)cols * (double)(((size_t)1 << w) - 2) + (double)chains * (double)e_bits + (double)nnz * nwin +
          (double)(chains - std::min(chains, rows));
 }
-int spmv_window(size_t rows, size_t cols, size_t nnz, size_t chains, int e_bits, size_t row_bytes) {
+// (extra_rows: rows of a column's table beyond 2^w -- 0, or 1 for the signed call's tables over [x ; x^-1]; only the cap sees them)
+static int spmv_window_with(size_t extra_rows, size_t rows, size_t cols, size_t nnz, size_t chains, int e_bits, size_t row_bytes) {
   const long forced = env_now("PGPU_SPMV_WINDOW");
   if (forced > 0) return (int)std::min(forced, 6L);
   int best = 1;
   double best_cost = spmv_products(rows, cols, nnz, chains, e_bits, 1);
   for (int w = 2; w <= 6; ++w) {
-    if ((double)cols * (double)((size_t)1 << w) * (double)row_bytes > (double)kMatvecTableCap) break;
+    if ((double)cols * (double)(((size_t)1 << w) + extra_rows) * (double)row_bytes > (double)kMatvecTableCap) break;
     const double cost = spmv_products(rows, cols, nnz, chains, e_bits, w);
     if (cost < best_cost) { best_cost = cost; best = w; }
   }
   return best;
+}
+int spmv_window(size_t rows, size_t cols, size_t nnz, size_t chains, int e_bits, size_t row_bytes) {
+  return spmv_window_with(0, rows, cols, nnz, chains, e_bits, row_bytes);
+}
+// the signed call: the unsigned counts (the signed table costs the same 2^w - 2 products, the Booth recoding has the same
+// digits) plus the inversion of EVERY column of x; the table is one row longer per column, which only the cap sees
+double spmv_signed_products(size_t rows, size_t cols, size_t nnz, size_t chains, int e_bits, int w) {
+  return spmv_products(rows, cols, nnz, chains, e_bits, w) + (double)invert_products(cols);
+}
+int spmv_signed_window(size_t rows, size_t cols, size_t nnz, size_t chains, int e_bits, size_t row_bytes) {
+  return spmv_window_with(1, rows, cols, nnz, chains, e_bits, row_bytes);
 }
 size_t spmv_chains_estimate(size_t rows, size_t nnz, size_t longest, int chunk) {
   const size_t c = (size_t)chunk, cut = [c](size_t m) { return std::max<size_t>(1, (m + c - 1) / c); }(longest);

@@ -210,6 +210,12 @@ using ConvPlan = MatmulPlan;   // tile / last: images of a pass
 size_t conv_slices(int G, size_t t, size_t n_o, size_t taps);
 double conv_products(int G, size_t n_img, size_t elems, size_t n_o, size_t taps, int e_bits, int w, size_t tile);
 void conv_plan(int G, size_t n_img, size_t elems, size_t n_o, size_t taps, int e_bits, size_t row_bytes, ConvPlan* plan);
+// The signed call (hensel_conv_signed.hpp; pgpu_batch_ct_conv2d_signed, pgpu_ct_conv2d_signed_plan): conv_plan with two
+// changes, the relation matmul_signed_plan has to matmul_plan -- the cap is held against the signed table,
+//     tile * elems * (2^w + 1) * row_bytes <= kMatvecTableCap,
+// and plan->products includes the one inversion of all n_img * elems elements (invert_products).  The per-pass counts, the
+// slice rule, the ties and the three knobs are conv_plan's.
+void conv_signed_plan(int G, size_t n_img, size_t elems, size_t n_o, size_t taps, int e_bits, size_t row_bytes, ConvPlan* plan);
 // the sizes of a shape d = {n_img, c_in, h, w, c_out, kh, kw, stride_h, stride_w, pad_h, pad_w} (the order of
 // pgpu_conv2d_shape).  false -- what both C-ABI calls refuse of a shape alone: a dimension or stride equal to 0, pad >=
 // kernel, kernel > padded image, an image or kernel side of 2^30 or more, a size product beyond size_t.
@@ -312,6 +318,12 @@ int spmv_levels(int chunk, size_t longest);
 //    under kMatvecTableCap.  PGPU_SPMV_WINDOW=w forces it.
 double spmv_products(size_t rows, size_t cols, size_t nnz, size_t chains, int e_bits, int w);
 int spmv_window(size_t rows, size_t cols, size_t nnz, size_t chains, int e_bits, size_t row_bytes);
+//    the signed call (hensel_spmv_signed.hpp; pgpu_batch_ct_spmv_signed, pgpu_ct_spmv_signed_plan): the same counts plus the
+//    inversion of EVERY column of x (invert_products(cols)), the window minimising the unsigned count among those whose
+//    table of cols * (2^w + 1) rows stays under the cap.  Chunk, chains and fold are the unsigned call's; PGPU_SPMV_WINDOW /
+//    _CHUNK force the signed call too.
+double spmv_signed_products(size_t rows, size_t cols, size_t nnz, size_t chains, int e_bits, int w);
+int spmv_signed_window(size_t rows, size_t cols, size_t nnz, size_t chains, int e_bits, size_t row_bytes);
 //    chains of a matrix of which only rows, nnz and the longest row are known (the plan call): the longest row cut by the
 //    chunk, the other rows taken as equally long -- exact while no row is longer than the chunk and for rows of one length,
 //    an estimate otherwise

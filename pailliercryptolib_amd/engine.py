@@ -255,15 +255,19 @@ class PublicKey:
         inner = n_vec if transposed else len(rows)
         return [out[k:k + inner] for k in range(0, len(out), inner)]
 
-    def conv2d(self, x, w, stride=1, padding=0, e_bits=None):
+    def conv2d(self, x, w, stride=1, padding=0, e_bits=None, signed=False):
         """Encrypted 2-D convolution: x nested lists [n_img][C_in][H][W] of ciphertexts (ints modulo n^2), w nested lists
-        [C_out][C_in][kh][kw] of non-negative ints, stride and padding an int or a (vertical, horizontal) pair -> nested
+        [C_out][C_in][kh][kw] of ints (non-negative, or of either sign with signed=True), stride and padding an int or a (vertical, horizontal) pair -> nested
         lists [n_img][C_out][OH][OW] of ciphertexts, OH = (H + 2 pad_h - kh) // stride_h + 1, OW likewise,
         out[n][co][oy][ox] = prod_{ci,ky,kx} x[n][ci][oy*stride_h + ky - pad_h][ox*stride_w + kx - pad_w]^w[co][ci][ky][kx]
         mod n^2 with taps outside the image left out (zero padding), i.e. encryptions of what
         torch.nn.functional.conv2d(m, w, stride=stride, padding=padding) computes, mod n.  One pgpu_batch_ct_conv2d call on
         resident batches (window tables per tile of images, addressed by the output position: no index list); there is
-        no element-wise fall-back and none through ``spmv``."""
+        no element-wise fall-back and none through ``spmv``.
+        signed=False: a negative weight is an error (it has no encoding; pass w mod n), e_bits defaults to the widest weight.
+        signed=True: a CNN filter as it is -- the weights are packed as two's complement in e_bits bits (default: the smallest
+        width that holds every one) and the one call is pgpu_batch_ct_conv2d_signed (x^-1 by one batched inversion, a table
+        over [x ; x^-1] per tile, Booth digits)."""
         def pair(v, what):
             p = (v, v) if isinstance(v, int) else tuple(v)
             if len(p) != 2 or any(int(q) != q or q < 0 for q in p):
@@ -288,27 +292,36 @@ class PublicKey:
         if kh > h + 2 * ph or kw > wd + 2 * pw:
             raise RuntimeError("conv2d error: the kernel exceeds the padded image")
         flat = [int(v) for f in ws for ch in f for row in ch for v in row]
-        if min(flat) < 0:
-            raise RuntimeError("conv2d error: negative weights have no encoding (pass w mod n)")
-        if e_bits is None:
-            e_bits = max(1, max(v.bit_length() for v in flat))
-        ew = (int(e_bits) + 63) // 64
+        call = _capi.lib().pgpu_batch_ct_conv2d
+        if signed:
+            e_bits, ew, flat = self._signed_weights(flat, e_bits)
+            call = _capi.lib().pgpu_batch_ct_conv2d_signed
+        else:
+            if min(flat) < 0:
+                raise RuntimeError("conv2d error: negative weights have no encoding (pass w mod n)")
+            if e_bits is None:
+                e_bits = max(1, max(v.bit_length() for v in flat))
+            ew = (int(e_bits) + 63) // 64
         oh, ow = (h + 2 * ph - kh) // sh + 1, (wd + 2 * pw - kw) // sw + 1
         shape = _capi.Conv2dShape(n_img, c_in, h, wd, c_out, kh, kw, sh, sw, ph, pw)
         cts = [c for img in xs for ch in img for row in ch for c in row]
         out = self._resident_call([self._ct(cts), (flat, ew)], n_img * c_out * oh * ow, lambda L, hd, o:
-                                  L.pgpu_batch_ct_conv2d(self._h, hd[0], hd[1], ctypes.byref(shape), int(e_bits), o))
+                                  call(self._h, hd[0], hd[1], ctypes.byref(shape), int(e_bits), o))
         it = iter(out)
         return [[[[next(it) for _ in range(ow)] for _ in range(oh)] for _ in range(c_out)] for _ in range(n_img)]
 
-    def spmv(self, x, indptr, indices, w, e_bits=None):
+    def spmv(self, x, indptr, indices, w, e_bits=None, signed=False):
         """Encrypted sparse matrix-vector product: x a list of ciphertexts (ints modulo n^2), the plaintext matrix in CSR
-        form -- indptr (rows + 1 offsets, starting at 0), indices (a column of x per entry), w (a non-negative int per
-        entry) -> the list of ciphertexts prod_t x[indices[t]]^w[t] mod n^2 over the entries t of every row, i.e.
+        form -- indptr (rows + 1 offsets, starting at 0), indices (a column of x per entry), w (an int per
+        entry: non-negative, or of either sign with signed=True) -> the list of ciphertexts prod_t x[indices[t]]^w[t] mod n^2 over the entries t of every row, i.e.
         encryptions of (A @ m) mod n; an empty row gives 1.  A weighted group-by SUM(v * x) GROUP BY id is the CSR with
         indices = argsort(ids, stable), w = v[indices], indptr = the running count of every id.  One pgpu_batch_ct_spmv
         call on resident batches (a shared-table multi-exponentiation per chain of a row); there is no element-wise
-        fall-back."""
+        fall-back.
+        signed=False: a negative weight is an error (it has no encoding; pass w mod n), e_bits defaults to the widest weight.
+        signed=True: a graph Laplacian as it is -- the weights are packed as two's complement in e_bits bits (default: the
+        smallest width that holds every one) and the one call is pgpu_batch_ct_spmv_signed, which inverts EVERY element of x:
+        a non-unit refuses the call also where no entry names its column."""
         indptr, indices, flat = [int(v) for v in indptr], [int(v) for v in indices], [int(v) for v in w]
         cols, rows = len(x), len(indptr) - 1
         if cols == 0 or rows < 1 or not flat or len(indices) != len(flat) or indptr[0] != 0 or indptr[-1] != len(flat):
@@ -317,14 +330,19 @@ class PublicKey:
             raise RuntimeError("spmv error: indptr must be non-decreasing")
         if min(indices) < 0 or max(indices) >= cols:
             raise RuntimeError("spmv error: a column index is not below len(x)")
-        if min(flat) < 0:
-            raise RuntimeError("spmv error: negative weights have no encoding (pass w mod n)")
-        if e_bits is None:
-            e_bits = max(1, max(v.bit_length() for v in flat))
-        ew = (int(e_bits) + 63) // 64
+        call = _capi.lib().pgpu_batch_ct_spmv
+        if signed:
+            e_bits, ew, flat = self._signed_weights(flat, e_bits)
+            call = _capi.lib().pgpu_batch_ct_spmv_signed
+        else:
+            if min(flat) < 0:
+                raise RuntimeError("spmv error: negative weights have no encoding (pass w mod n)")
+            if e_bits is None:
+                e_bits = max(1, max(v.bit_length() for v in flat))
+            ew = (int(e_bits) + 63) // 64
         rp, ci = np.array(indptr, dtype=np.uint64), np.array(indices, dtype=np.uint32)
         return self._resident_call([self._ct(x), (flat, ew)], rows, lambda L, h, out:
-                                   L.pgpu_batch_ct_spmv(self._h, h[0], _ptr(rp), _ptr(ci), h[1], rows, int(e_bits), out))
+                                   call(self._h, h[0], _ptr(rp), _ptr(ci), h[1], rows, int(e_bits), out))
 
     def weighted_sum(self, xs, w=None):
         """Encrypted weighted sum across K batches: xs a list of K lists of ciphertexts (ints modulo n^2), all of one
