@@ -33,6 +33,16 @@
 #ifndef PGPU_PSB_DOUBLED
 #define PGPU_PSB_DOUBLED 1
 #endif
+// 1 (default): the single product of two independent operands -- a2 * b of a pair squaring (doubled form), a * c of a pair
+// product -- is split in the middle (Karatsuba): 3 * 18^2 = 972 limb products instead of 1296 for 36 limb subtractions and 140
+// 64-bit adds, 196 / 163 instructions fewer per pair squaring / pair product.  The same column sums in another order, so the
+// same digits and limbs, bit for bit; partial sums may wrap modulo 2^64 and the wraps cancel.  The symmetric product, the
+// two-product scan, the reductions, the entry and the exit keep the schoolbook form.  0: the schoolbook product everywhere
+// (A/B: tools/ubench_ps.hip has both forms as template arguments; profiles/ps_karatsuba.txt).  Model:
+// tests/test_ps_karatsuba_model.py.
+#ifndef PGPU_PSB_KARATSUBA
+#define PGPU_PSB_KARATSUBA 1
+#endif
 
 namespace pgpu {
 
@@ -48,6 +58,11 @@ __device__ __forceinline__ void psb_mac_pinned(int64_t& acc, int32_t x, int32_t 
   asm volatile("" ::"v"(acc));
 }
 
+// ... where the partial sum may wrap modulo 2^64 (the Karatsuba joins): the same instruction, no signed overflow in the source
+__device__ __forceinline__ void psb_mac_wrap(int64_t& acc, int32_t x, int32_t y) {
+  acc = (int64_t)((uint64_t)acc + (uint64_t)((int64_t)x * y));
+}
+
 // a column of 3K products of limbs up to 2^(LB-1), the digit step's q * n_0 and the recorded digit: inside int64_t
 template <int K, int LB>
 struct PsbFits {
@@ -61,17 +76,31 @@ struct PsbFits {
 // fits K balanced limbs (then the carry out of the top column is zero).  r may be x2 or y1.
 // DBL (with SYM): x1 holds 2 * y1, |limb| <= 2^LB.  The pairs i < j are x1[i] * y1[j], the diagonal y1[i]^2, all on the one
 // accumulator: a column is at most 18 products of 2^(2LB-1), one square and K q*n terms -- 73 * 2^56 at K = 36, LB = 29.
-template <int K, int LB, int NP, bool SYM, int QMODE, bool DBL = false>
+// KARA (single product, not SYM, K even): the operand products in the Karatsuba form, |x1 limb| <= 2^LB, |y1 limb| <= 2^(LB-1):
+// the differences of the halves fit int32_t (2^(LB+1), 2^LB), a half product's column sum is at most 18 * 2^(2LB-1) < 2^63.
+template <int K, int LB, int NP, bool SYM, int QMODE, bool DBL = false, bool KARA = false>
 __device__ __forceinline__ void psb_montmul(int32_t (&r)[K], const int32_t (&x1)[K], const int32_t (&y1)[K],
                                             const int32_t (&x2)[K], const int32_t (&y2)[K], const int32_t (&n)[K],
                                             uint32_t n0inv, int32_t (&qio)[K]) {
   static_assert(!(SYM && NP != 1), "a symmetric product is a single one");
   static_assert(SYM || !DBL, "the doubled operand belongs to the symmetric product");
+  static_assert(!KARA || (NP == 1 && !SYM && K % 2 == 0), "the split serves the single product of two operands, in two halves");
   static_assert(PsbFits<K, LB>::value, "a column sums up to 3K products below 2^(2(LB-1)): must stay below 2^63");
+  constexpr int H = K / 2;
   int32_t q[K];
   int64_t acc = 0;
   int32_t onev = 1;
   asm("" : "+v"(onev));   // (keeps "+= 32-bit value" ONE v_mad_i64_i32 instead of a sign extension and an add)
+  // KARA: the differences of the halves, and the column sums of the low and the high half products while they wait
+  int32_t dx[KARA ? H : 1], dy[KARA ? H : 1];
+  uint64_t lo[KARA ? 2 * H - 1 : 1], hi[KARA ? 2 * H - 1 : 1];
+  if constexpr (KARA) {
+#pragma unroll
+    for (int j = 0; j < H; ++j) {
+      dx[j] = x1[j] - x1[H + j];
+      dy[j] = y1[H + j] - y1[j];
+    }
+  }
   ps_static_for<2 * K>([&](auto colc) __attribute__((always_inline)) {
     constexpr int col = decltype(colc)::value;
     // ---- q_i * n_j of the digits found so far, j >= 1 (n_0 belongs to the digit step), onto the carry of the column below
@@ -109,6 +138,40 @@ __device__ __forceinline__ void psb_montmul(int32_t (&r)[K], const int32_t (&x1)
         }
         if constexpr (col % 2 == 0) psb_mac(acc, x1[col / 2], x1[col / 2]);
       }
+    } else if constexpr (KARA) {
+      // x = x0 + x1 B^H, y = y0 + y1 B^H:  x y = L + (L + Hh + M) B^H + Hh B^2H  with L = x0 y0, Hh = x1 y1 and
+      // M = (x0 - x1)(y1 - y0) -- 3 H^2 products.  The column sums L_k, Hh_k are chains of their own from a zero addend
+      // (L_k waits from column k to k + H, Hh_k from k + H to k + 2H); the M products go straight onto the accumulator.
+      // Everything here is wrapping 64-bit arithmetic (a partial sum of the M products may pass 2^63 where they land before
+      // the join; the wraps cancel): the finished column is the schoolbook column.
+      if constexpr (col <= 2 * H - 2) {
+        constexpr int ilo = col < H ? 0 : col - H + 1;
+        constexpr int ihi = col < H ? col + 1 : H;
+        int64_t s = 0;
+        ps_static_for<ihi - ilo>([&](auto ic) __attribute__((always_inline)) {
+          constexpr int i = ilo + decltype(ic)::value;
+          psb_mac_wrap(s, x1[i], y1[col - i]);
+        });
+        lo[col] = (uint64_t)s;
+        acc = (int64_t)((uint64_t)acc + lo[col]);
+      }
+      if constexpr (col >= H && col <= 3 * H - 2) {
+        constexpr int k = col - H;
+        constexpr int ilo = k < H ? 0 : k - H + 1;
+        constexpr int ihi = k < H ? k + 1 : H;
+        int64_t s = 0;
+        ps_static_for<ihi - ilo>([&](auto ic) __attribute__((always_inline)) {
+          constexpr int i = ilo + decltype(ic)::value;
+          psb_mac_wrap(s, x1[H + i], y1[H + k - i]);
+        });
+        hi[k] = (uint64_t)s;
+        acc = (int64_t)((uint64_t)acc + (lo[k] + hi[k]));
+        ps_static_for<ihi - ilo>([&](auto ic) __attribute__((always_inline)) {
+          constexpr int i = ilo + decltype(ic)::value;
+          psb_mac_wrap(acc, dx[i], dy[k - i]);
+        });
+      }
+      if constexpr (col >= 2 * H && col <= 4 * H - 2) acc = (int64_t)((uint64_t)acc + hi[col - 2 * H]);
     } else {
       constexpr int ilo = col < K ? 0 : col - K + 1;
       constexpr int ihi = col < K ? col + 1 : K;
@@ -145,7 +208,8 @@ __device__ __forceinline__ const uint32_t (&psb_bits(const int32_t (&v)[K]))[K] 
 // (a, b) = (a, b)^2 (ps_pairsqr):  t = a*a with its digits q;  b = (2*a*b + q) reduced;  a = t.   |2b| <= 2^LB fits int32_t
 // DBL: a2 = 2a serves both products (|2a| <= 2^LB as well): t = sym(a2, a), b = (a2*b + q) reduced -- the same column sums in
 // another order of summation, so the same digits and the same limbs, bit for bit.
-template <int K, int LB, bool DBL = (PGPU_PSB_DOUBLED != 0)>
+// KARA (with DBL): the b part's a2 * b in the Karatsuba form of psb_montmul.
+template <int K, int LB, bool DBL = (PGPU_PSB_DOUBLED != 0), bool KARA = (PGPU_PSB_KARATSUBA != 0)>
 __device__ __forceinline__ void psb_pairsqr(int32_t (&a)[K], int32_t (&b)[K], const int32_t (&n)[K], uint32_t n0inv) {
   int32_t qd[K], t[K];
   if constexpr (DBL) {
@@ -153,7 +217,7 @@ __device__ __forceinline__ void psb_pairsqr(int32_t (&a)[K], int32_t (&b)[K], co
 #pragma unroll
     for (int j = 0; j < K; ++j) a2[j] = a[j] * 2;
     psb_montmul<K, LB, 1, true, 1, true>(t, a2, a, a2, a, n, n0inv, qd);
-    psb_montmul<K, LB, 1, false, 2>(b, a2, b, a2, b, n, n0inv, qd);
+    psb_montmul<K, LB, 1, false, 2, false, KARA>(b, a2, b, a2, b, n, n0inv, qd);
   } else {
     psb_montmul<K, LB, 1, true, 1>(t, a, a, a, a, n, n0inv, qd);
 #pragma unroll
@@ -165,7 +229,9 @@ __device__ __forceinline__ void psb_pairsqr(int32_t (&a)[K], int32_t (&b)[K], co
 }
 
 // (a, b) = (a, b) (x) (c, d) (ps_pairmul: b waits in LDS through the first product, t through the second)
-template <int K, int LB>
+// KARA: the first product a * c in the Karatsuba form (balanced operands: the window loop and the table build; the entry and
+// the exit, whose limbs are relaxed sums and which run once, pass false)
+template <int K, int LB, bool KARA = (PGPU_PSB_KARATSUBA != 0)>
 __device__ __forceinline__ void psb_pairmul(int32_t (&a)[K], int32_t (&b)[K], const int32_t (&c)[K], const int32_t (&d)[K],
                                             const int32_t (&n)[K], uint32_t n0inv, uint4* slot) {
   int32_t qd[K];
@@ -173,7 +239,7 @@ __device__ __forceinline__ void psb_pairmul(int32_t (&a)[K], int32_t (&b)[K], co
     int32_t t[K];
     ps_park_store<K>(slot, psb_bits<K>(b));
     __builtin_amdgcn_sched_barrier(0);
-    psb_montmul<K, LB, 1, false, 1>(t, a, c, a, c, n, n0inv, qd);
+    psb_montmul<K, LB, 1, false, 1, false, KARA>(t, a, c, a, c, n, n0inv, qd);
     __builtin_amdgcn_sched_barrier(0);
     ps_park_swap<K>(slot, psb_bits<K>(b), psb_bits<K>(t));
     __builtin_amdgcn_sched_barrier(0);
@@ -267,7 +333,7 @@ __device__ __forceinline__ void psb_entry_from_pair_row(const HenselArgs& A, int
     psb_relimb<K, LB, NI>(zl, zb);
     psb_mul<K, LB>(tb, zl, cb, n, n0inv);
     psb_relimb<K, LB, NI>(a, za);
-    psb_pairmul<K, LB>(a, b, ma, mb, n, n0inv, slot);
+    psb_pairmul<K, LB, false>(a, b, ma, mb, n, n0inv, slot);
     psb_add<K, LB>(b, tb);
     psb_add<K, LB>(acc_a, a);
     psb_add<K, LB>(acc_b, b);
@@ -295,7 +361,7 @@ __device__ __forceinline__ void psb_exit_words(const HenselArgs& A, int side, si
     ma[j] = (int32_t)HCTX(h)[j];
     mb[j] = 0;
   }
-  psb_pairmul<K, LB>(a, b, ma, mb, n, n0inv, slot);
+  psb_pairmul<K, LB, false>(a, b, ma, mb, n, n0inv, slot);
   uint32_t u0[K], u1[K];
   const int32_t neg_a = psb_canon<K, LB>(u0, a);             // -1: a' < 0
 #pragma unroll

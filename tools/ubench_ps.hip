@@ -14,6 +14,8 @@
 // in this binary -- one squaring and `build` products, then nwin windows (the top one of `half` squarings) of w squarings and one
 // product that stands after w - ctz(digit) of them, the digits a fixed pseudo-random sequence in SGPRs, the loop shape that of
 // hensel_decrypt_psb_kernel (one body of each operation, wave-uniform branches).
+// Fifth part (the Karatsuba split of the single products): exp_kernel_bal<..., KARA = true> runs psb_pairsqr / psb_pairmul with the
+// a2*b and a*c products split in the middle next to the schoolbook form, the odd-table loop shape, the parent's form first and last.
 // Reported in shader cycles per exponentiation (no instruction count needed).
 // build: python tools/build_ubench.py ubench_ps -I<repo>/pailliercryptolib_amd/csrc [-DPGPU_PS_SPLIT=1]   (the library's compile step, alignment pass included)
 #include <hip/hip_runtime.h>
@@ -103,7 +105,7 @@ __global__ __launch_bounds__(256, MINW) void sq_kernel_bal(const uint32_t* in, c
 
 // one exponentiation's operations on balanced limbs: `build` times ([a squaring if half] + a product), then `nwin` times
 // (w squarings + [a product if do_mul]); DBL: the pair squaring on the doubled operand
-template <int K, int LB, int MINW, bool DBL, bool ODD = false>
+template <int K, int LB, int MINW, bool DBL, bool ODD = false, bool KARA = false>
 __global__ __launch_bounds__(256, MINW) void exp_kernel_bal(const uint32_t* in, const uint32_t* nn, uint32_t* out,
                                                             unsigned long long* cyc, uint32_t n0inv_in, int build, int half,
                                                             int nwin, int w, int do_mul) {
@@ -125,7 +127,7 @@ __global__ __launch_bounds__(256, MINW) void exp_kernel_bal(const uint32_t* in, 
     // `half` holds the squarings of the top window here.  Table: trip 0 squares, trips 1 .. build multiply
 #pragma unroll 1
     for (int e = 0; e <= build; ++e) {
-      if (e == 0) psb_pairsqr<K, LB, DBL>(a, b, n, n0inv);
+      if (e == 0) psb_pairsqr<K, LB, DBL, KARA>(a, b, n, n0inv);
       __builtin_amdgcn_sched_barrier(0);
       if (e > 0) {
 #pragma unroll
@@ -133,7 +135,7 @@ __global__ __launch_bounds__(256, MINW) void exp_kernel_bal(const uint32_t* in, 
           c[j] = (int32_t)(in[(size_t)lane * 2 * K + j] ^ (e & 1));
           d[j] = (int32_t)(in[(size_t)lane * 2 * K + K + j] ^ (e & 2));
         }
-        psb_pairmul<K, LB>(a, b, c, d, n, n0inv, slot);
+        psb_pairmul<K, LB, KARA>(a, b, c, d, n, n0inv, slot);
       }
     }
 #pragma unroll 1
@@ -150,33 +152,33 @@ __global__ __launch_bounds__(256, MINW) void exp_kernel_bal(const uint32_t* in, 
             c[j] = (int32_t)(in[(size_t)lane * 2 * K + j] ^ (idx & 1));
             d[j] = (int32_t)(in[(size_t)lane * 2 * K + K + j] ^ (idx & 2));
           }
-          psb_pairmul<K, LB>(a, b, c, d, n, n0inv, slot);
+          psb_pairmul<K, LB, KARA>(a, b, c, d, n, n0inv, slot);
         }
-        if (i < wl) psb_pairsqr<K, LB, DBL>(a, b, n, n0inv);
+        if (i < wl) psb_pairsqr<K, LB, DBL, KARA>(a, b, n, n0inv);
       }
     }
   } else {
 #pragma unroll 1
   for (int e = 0; e < build; ++e) {
-    if (half) psb_pairsqr<K, LB, DBL>(a, b, n, n0inv);
+    if (half) psb_pairsqr<K, LB, DBL, KARA>(a, b, n, n0inv);
 #pragma unroll
     for (int j = 0; j < K; ++j) {
       c[j] = (int32_t)(in[(size_t)lane * 2 * K + j] ^ (e & 1));
       d[j] = (int32_t)(in[(size_t)lane * 2 * K + K + j] ^ (e & 2));
     }
-    psb_pairmul<K, LB>(a, b, c, d, n, n0inv, slot);
+    psb_pairmul<K, LB, KARA>(a, b, c, d, n, n0inv, slot);
   }
 #pragma unroll 1
   for (int wi = 0; wi < nwin; ++wi) {
 #pragma unroll 1
-    for (int i = 0; i < w; ++i) psb_pairsqr<K, LB, DBL>(a, b, n, n0inv);
+    for (int i = 0; i < w; ++i) psb_pairsqr<K, LB, DBL, KARA>(a, b, n, n0inv);
     if (do_mul) {
 #pragma unroll
       for (int j = 0; j < K; ++j) {
         c[j] = (int32_t)(in[(size_t)lane * 2 * K + j] ^ (wi & 1));
         d[j] = (int32_t)(in[(size_t)lane * 2 * K + K + j] ^ (wi & 2));
       }
-      psb_pairmul<K, LB>(a, b, c, d, n, n0inv, slot);
+      psb_pairmul<K, LB, KARA>(a, b, c, d, n, n0inv, slot);
     }
   }
   }
@@ -189,7 +191,7 @@ __global__ __launch_bounds__(256, MINW) void exp_kernel_bal(const uint32_t* in, 
   }
 }
 
-template <int K, int LB, bool DBL, bool ODD = false>
+template <int K, int LB, bool DBL, bool ODD = false, bool KARA = false>
 void run_exp(const char* name, int blocks, unsigned lds, int build, int half, int nwin, int w, int do_mul) {
   const size_t lanes = (size_t)blocks * 256, waves = lanes / 64;
   std::vector<uint32_t> h(lanes * 2 * K), hn(K);
@@ -206,13 +208,13 @@ void run_exp(const char* name, int blocks, unsigned lds, int build, int half, in
   hipMalloc(&din, h.size() * 4); hipMalloc(&dn, hn.size() * 4); hipMalloc(&dout, h.size() * 4); hipMalloc(&dcyc, waves * 8);
   hipMemcpy(din, h.data(), h.size() * 4, hipMemcpyHostToDevice);
   hipMemcpy(dn, hn.data(), hn.size() * 4, hipMemcpyHostToDevice);
-  if (lds) hipFuncSetAttribute((const void*)exp_kernel_bal<K, LB, 1, DBL, ODD>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+  if (lds) hipFuncSetAttribute((const void*)exp_kernel_bal<K, LB, 1, DBL, ODD, KARA>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
   hipEvent_t e0, e1;
   hipEventCreate(&e0); hipEventCreate(&e1);
   std::vector<unsigned long long> cyc(waves);
   for (int rep = 0; rep < 4; ++rep) {
     hipEventRecord(e0);
-    hipLaunchKernelGGL((exp_kernel_bal<K, LB, 1, DBL, ODD>), dim3(blocks), dim3(256), lds, 0, din, dn, dout, dcyc, n0inv, build, half, nwin, w, do_mul);
+    hipLaunchKernelGGL((exp_kernel_bal<K, LB, 1, DBL, ODD, KARA>), dim3(blocks), dim3(256), lds, 0, din, dn, dout, dcyc, n0inv, build, half, nwin, w, do_mul);
     hipEventRecord(e1);
     hipEventSynchronize(e1);
     float ms = 0;
@@ -223,8 +225,8 @@ void run_exp(const char* name, int blocks, unsigned lds, int build, int half, in
     for (auto v : cyc) mean += (double)v;
     mean /= waves;
     const int sq = ODD ? 1 + (nwin - 1) * w + half : (half ? build : 0) + nwin * w, mul = build + (do_mul ? nwin : 0);
-    if (rep) printf("%-52s doubled=%d  %4d squarings + %3d products  wall %7.3f ms | cycles per exponentiation: mean %.5g (min %.5g max %.5g)"
-                    " | clock held %.3f GHz\n", name, (int)DBL, sq, mul, ms, mean, (double)cyc.front(), (double)cyc.back(),
+    if (rep) printf("%-52s doubled=%d karatsuba=%d  %4d squarings + %3d products  wall %7.3f ms | cycles per exponentiation: mean %.5g (min %.5g max %.5g)"
+                    " | clock held %.3f GHz\n", name, (int)DBL, (int)KARA, sq, mul, ms, mean, (double)cyc.front(), (double)cyc.back(),
                     (double)cyc.back() / (ms * 1e6));
   }
   hipFree(din); hipFree(dn); hipFree(dout); hipFree(dcyc);
@@ -320,5 +322,12 @@ int main(int argc, char** argv) {
   run_exp<36, 29, false>("squarings alone", 64, 84000, 0, 0, 170, 6, 0);
   run_exp<36, 29, true>("squarings alone", 64, 84000, 0, 0, 170, 6, 0);
   run_exp<36, 29, false>("parent again: w=5, chained table (30 products)", 64, 84000, 30, 0, 204, 5, 1);
+  // the Karatsuba split of a2*b (pair squaring) and a*c (pair product), hensel_ps_bal.hpp KARA: the schoolbook form first and last
+  printf("# Karatsuba split of the single products: w=6, odd-power table, lone quarter chip (64 WGs, CU claim, MINW=1)\n");
+  run_exp<36, 29, true, true, false>("schoolbook single products (parent)", 64, 84000, 31, 4, 171, 6, 1);
+  run_exp<36, 29, true, true, true>("Karatsuba a2*b and a*c", 64, 84000, 31, 4, 171, 6, 1);
+  run_exp<36, 29, true, true, false>("schoolbook single products (parent)", 64, 84000, 31, 4, 171, 6, 1);
+  run_exp<36, 29, true, true, true>("Karatsuba a2*b and a*c", 64, 84000, 31, 4, 171, 6, 1);
+  run_exp<36, 29, true, true, false>("schoolbook single products (parent again)", 64, 84000, 31, 4, 171, 6, 1);
   return 0;
 }
