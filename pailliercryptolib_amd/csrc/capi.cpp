@@ -1736,6 +1736,8 @@ int host_busy(rt::Device& dev, int lane, size_t count = (size_t)-1) {
 std::atomic<int> g_ps_balanced{[] { const char* e = std::getenv("PGPU_PS_BALANCED"); return e && std::atoi(e) == 0 ? 0 : 1; }()};
 // table entries per wavefront of the last one-lane decrypt launch (pgpu_debug_last_ps_table_entries: tests see which table form ran)
 std::atomic<int> g_last_ps_table_entries{0};
+// digit form of the last one-wavefront decrypt launch (pgpu_debug_last_wave_wide): 1 = 32-bit quotient digits, 0 = LB-bit ones, -1 = none yet
+std::atomic<int> g_last_wave_wide{-1};
 const pgpu_privkey::HenselSet* ps_balanced_set(const pgpu_privkey* key, int pair_l2) {
   return (g_ps_balanced.load() && key->hs_psb && key->hs_psb->pair_l2 == pair_l2) ? key->hs_psb.get() : nullptr;
 }
@@ -1868,6 +1870,7 @@ int decrypt_on(rt::Device& d, const pgpu_privkey* key, const uint64_t* d_c, uint
       // 17 P instead of 2 P, which needs R = 2^(lb K) >= 2^10 P; P = p k < 2^(exp_bits + lb)  (3072-bit keys: R >= 16 P only)
       static const bool wide_ok = [] { const char* e = getenv("PGPU_WAVE_WIDEQ"); return !e || atoi(e) != 0; }();
       const bool wide = wide_ok && hset->lb * hset->K - (key->exp_bits + hset->lb) >= 10;
+      g_last_wave_wide.store(wide ? 1 : 0);
       if (!pgpu::launch_hensel_wave(hset->K, hset->lb, wide, h, s))
         return fail(PGPU_ERR_UNSUPPORTED, "wavefront-wide decrypt kernel not compiled");
     } else if (psf) {
@@ -2452,6 +2455,9 @@ int pgpu_debug_set_ps_odd_table(int on) { return pgpu::policy::set_ps_odd_table(
 // ... and the window-table entries per wavefront of the last one-lane decrypt launch of this process: 2^w for the
 // half-squared table and under the masked policy, 2^(w-1) + 1 for the odd powers; 0: no such launch yet
 int pgpu_debug_last_ps_table_entries(void) { return g_last_ps_table_entries.load(); }
+// ... and the digit form of the last one-wavefront decrypt launch of this process (hensel_wave.hpp: WIDEQ): 1 = whole-word
+// quotient digits, 0 = LB-bit digits; -1: no such launch yet
+int pgpu_debug_last_wave_wide(void) { return g_last_wave_wide.load(); }
 // tests / A-B measurements: PGPU_FIXED_WINDOW from inside the process (1..6 forces, 0: by the rules); returns what was set
 int pgpu_debug_set_fixed_window(int w) { return pgpu::policy::set_fixed_window(w); }
 // ... and the window a CRT decrypt of that exponent length and table entry size takes (one_lane: the one-lane forms)

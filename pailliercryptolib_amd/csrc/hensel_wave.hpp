@@ -255,6 +255,12 @@ __global__ __launch_bounds__(kWGThreads, 1) void hensel_decrypt_wave_kernel(Hens
     if ((r & 1) == 0) a += in ? buf[(size_t)r * wv_pair_words<K>() + lk] : 0u;
     b += in ? buf[(size_t)r * wv_pair_words<K>() + K + lk] : 0u;
   }
+  // ... but not as an entry of the table: a limb of b sums 2 * pchunks canonical ones -- up to 6 * 2^29 at <19,29> --, and a
+  // squaring doubles its b operand in 32 bits.  The main loop starts from entry 1 where the exponent's top window holds a lone
+  // bit (exp_bits == 1 mod w: 490-bit primes under the masked policy's 3-bit windows).  One carry step leaves the relaxed limbs
+  // every product leaves (the sums are below 10 P < R: no carry leaves limb K - 1)
+  a = wv_finish<LB>((uint64_t)a);
+  b = wv_finish<LB>((uint64_t)b);
   // ---- window table: entry 0 = one, entry 1 = base, entry e = entry e-1 times base ----
   const uint32_t ba = a, bb = b;
   entry_store(1, a, b);

@@ -251,6 +251,11 @@ def keys():
             found.append(v)
         v -= 2
     out["worst1040"] = (found[1], found[0])
+    # the edges of the 2048-bit class (gen_ps_edge_primes.py): the narrowest and the widest primes the unsigned <38,28> kernel
+    # serves beside this one, uneven pairs, and primes whose balanced limbs are nearly all zero / all of the largest magnitude
+    for c in json.load(open(os.path.join(GOLD, "ps_edge_primes.json")))["cases"]:
+        if c["name"].startswith("c2048-"):
+            out[c["name"]] = (int(c["p"], 16), int(c["q"], 16))
     return out
 
 
@@ -258,10 +263,19 @@ KEYS = keys()
 
 
 def test_key_fixture_covers_the_issue_list():
-    assert sorted(KEYS) == ["2037", "2051", "2052", "iso", "worst1040"]
+    assert sorted(KEYS) == ["2037", "2051", "2052", "c2048-heavy", "c2048-low", "c2048-tight", "c2048-uneven-low", "c2048-uneven-top",
+                            "iso", "worst1040"]
     for name, (p, q) in KEYS.items():
         assert max(p.bit_length(), q.bit_length()) <= FIT_BITS, name
     assert KEYS["worst1040"][0].bit_length() == FIT_BITS
+    widths = {name: tuple(sorted(v.bit_length() for v in KEYS[name])) for name in KEYS if name.startswith("c2048-")}
+    assert widths == {"c2048-low": (1005, 1005), "c2048-tight": (1032, 1032), "c2048-uneven-top": (1018, 1032),
+                      "c2048-uneven-low": (980, 1005), "c2048-heavy": (1024, 1024)}
+    for v in KEYS["c2048-tight"]:                           # 2^1032 - j 2^28 + 1: balanced limbs nearly all zero
+        assert sum(1 for x in limbs(v) if x == 0) >= 30
+    for v in KEYS["c2048-heavy"]:                           # ... and limbs 0 .. 34 all of the largest magnitude
+        assert all(abs(x) >= HALF - (1 << 16) for x in limbs(v)[:35])
+    assert limbs(min(KEYS["c2048-uneven-low"]))[34:] == [0, 0]            # zero top limbs on one side
 
 
 @pytest.mark.parametrize("name", sorted(KEYS))

@@ -186,7 +186,7 @@ def test_random_balanced_operands(qmode):
         check_against_schoolbook(x, y, N_MAX, N0_MAX, qin=qin)
 
 
-@pytest.mark.parametrize("name", ["iso", "2051", "worst1040"])
+@pytest.mark.parametrize("name", ["iso", "2051", "worst1040", "c2048-tight", "c2048-heavy"])
 def test_values_at_the_settled_size(name):
     """|value| near 0.54 p, both signs: where the window loop's values settle"""
     p = KEYS[name][0]
@@ -253,7 +253,7 @@ def pairmul(side, al, bl, cl, dl):
     return t, w
 
 
-@pytest.mark.parametrize("name", ["iso", "2051", "worst1040"])
+@pytest.mark.parametrize("name", ["iso", "2051", "worst1040", "c2048-tight", "c2048-heavy"])
 def test_pair_squaring_and_pair_product_against_pow(name):
     p = KEYS[name][0]
     side = Side(p, 0, 0)

@@ -151,7 +151,7 @@ def _ciphertexts(n, rng):
     return [1, n2 - 1, n + 1, rng.randrange(n2), pow(rng.randrange(2, n), n, n2) * (1 + n * 12345) % n2]
 
 
-@pytest.mark.parametrize("name", ["iso", "2037", "2051", "crafted", "even-top", "worst1040"])
+@pytest.mark.parametrize("name", ["iso", "2037", "2051", "crafted", "even-top", "worst1040", "c2048-tight", "c2048-heavy"])
 def test_odd_table_exponentiation_is_pow_and_stays_inside_the_limbs(name):
     if name == "crafted":
         p, q = sorted((crafted_prime(1024, "zero-digits"), crafted_prime(1024, "zero-digits-q")))
