@@ -34,6 +34,10 @@ CipherText packSlots(const CipherText& x, std::size_t seg_len, std::size_t slot_
 // include/ipcl/ext/arith.hpp
 CipherText negate(const CipherText& x);
 CipherText subtract(const CipherText& a, const CipherText& b);
+// include/ipcl/ext/index.hpp
+CipherText gather(const std::vector<const CipherText*>& xs, const std::vector<uint64_t>& idx);
+CipherText concat(const std::vector<const CipherText*>& xs);
+CipherText slice(const CipherText& x, std::size_t start, std::size_t count, std::size_t step);
 }
 
 class CipherText : public BaseText {
@@ -53,6 +57,9 @@ class CipherText : public BaseText {
 
   CipherText getCipherText(const size_t& idx) const;
   std::shared_ptr<PublicKey> getPubKey() const;
+  // (a text whose current copy is the device's is rotated there -- one pgpu_batch_gather -- and the result stays resident;
+  // same checks, messages and values as the host path, which a text with a current host copy still takes, and every text
+  // on a pool of more than one GPU, where the gather is not available)
   CipherText rotate(int shift) const;
 
   void save(serializer::OutputArchive& ar) const;   // reference ciphertext.hpp:69-74: base, "pk"
@@ -106,6 +113,13 @@ class CipherText : public BaseText {
   friend CipherText ext::subtract(const CipherText& a, const CipherText& b);
   // this[i] * b[i]^-1 mod n^2 (b == null: this[i]^-1), all inverses from one modular inversion: csrc/host/arith.cpp
   CipherText inverseMap(const CipherText* b) const;
+  friend CipherText ext::gather(const std::vector<const CipherText*>& xs, const std::vector<uint64_t>& idx);
+  friend CipherText ext::concat(const std::vector<const CipherText*>& xs);
+  friend CipherText ext::slice(const CipherText& x, std::size_t start, std::size_t count, std::size_t step);
+  // rows of the texts xs put end to end, re-indexed on the device: idx != null: row (*idx)[i]; step == 0: all of them
+  // (concat); else rows start, start + step, ..., count of them: csrc/host/index.cpp
+  static CipherText indexMap(const char* what, const std::vector<const CipherText*>& xs, const std::vector<uint64_t>* idx,
+                             std::size_t start, std::size_t count, std::size_t step);
   CipherText(const PublicKey& pk, std::shared_ptr<detail::DeviceBatch> dev);
   CipherText(std::shared_ptr<PublicKey> pk, std::shared_ptr<detail::DeviceBatch> dev);
   std::shared_ptr<PublicKey> m_pk;

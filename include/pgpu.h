@@ -53,6 +53,8 @@
  * multiplication, also for zero digits, so the duration does not depend on the key.  Under
  * pgpu_set_table_gather_policy(1) those kernels keep the full table and the fixed order (w squarings,
  * then the multiplication): a digit-independent instruction order.  Sliding windows stay opt-in.
+ * pgpu_batch_gather / _concat / _slice are NOT refused under the masked policy: the address stream depends on the
+ * caller's plaintext indices only, as for upload and download.
  * Device copies of private-key constants are zeroed before they are freed.
  *
  * ERRORS.  Every function returns PGPU_OK (0) or a negative pgpu_status; nothing calls
@@ -697,6 +699,46 @@ int pgpu_ct_conv2d_signed_plan(int key_bits, const pgpu_conv2d_shape* shape, int
 int pgpu_ct_spmv_signed_plan(int key_bits, size_t rows, size_t cols, size_t nnz, size_t longest_row, int e_bits,
                              int* window, int* chunk, int* levels, size_t* table_bytes, size_t* products);
 
+/* ---- re-indexing of resident batches: gather, concat, slice ----
+ * Between two calls on resident batches a caller picks rows, puts batches end to end or cuts a result into parts without
+ * leaving the device: a minibatch drawn from a resident data set, K clients' uploads stacked for pgpu_batch_ct_segment_sum,
+ * a layer's output split or permuted.  The calls take no key and preserve the domain: they move rows as BYTES, so they work
+ * on any batch -- plain uploaded words of any width (plaintext and randomness batches with words = 1 included), Montgomery
+ * words, pair rows -- and the result is what the sources are.  THERE IS NO CONVERSION INSIDE THESE CALLS: all sources of
+ * one call share one layout -- the same words, the same domain and, for pair rows or Montgomery words, the same context
+ * (modulus and form) -- and a call that mixes layouts is PGPU_ERR_INVALID_PARAM.  A caller who holds uploaded ciphertext
+ * words beside pair rows passes the uploaded batch through any ciphertext operation first, or gathers before mixing.
+ *
+ * pgpu_batch_gather: out[i] = row idx[i] of the concatenation of xs[0 .. n_src), n_out rows.  The same handle may appear
+ * twice (it is then two stretches of the concatenation); indices may repeat and come in any order; idx is HOST memory,
+ * consumed before the call returns.  PGPU_GATHER_ONE as an index yields the value 1 in the batch's domain -- the integer
+ * 1, R mod N, or the pair row of one that the key's pair form holds: a ciphertext there decrypts to 0 (zero padding for an
+ * im2col, a missing value).  One launch of row_gather_kernel (kind PGPU_KERNEL_GATHER): a row is read by neighbouring
+ * lanes in contiguous 16-byte pieces (8-byte where the row size is no multiple of 16), several rows in flight per
+ * wavefront (pgpu_batch_gather_plan reports the shape).
+ * pgpu_batch_concat: gather with the identity index, done as one stream-ordered device-to-device copy per source, with
+ * no index list and no kernel.
+ * pgpu_batch_slice: rows start, start + step, ..., count of them.  step == 1 is one copy; step > 1 takes the kernel (the
+ * strided read of an [n_vec][cols] batch as a column: start = column, step = cols, count = n_vec).
+ * The result is an ordinary immutable resident batch on the lane of xs[0] (of x); sources on other lanes are ordered in by
+ * the events pgpu_batch_ct_add uses.  Sources may be destroyed as soon as the call returns.
+ * PGPU_ERR_INVALID_PARAM: null or stale handles, a null out (or idx); n_src == 0 or above 65535; n_out == 0; an index at or
+ * beyond the total count that is not the sentinel (the message names the first offending position); a source of 2^32 - 1
+ * rows or more; step == 0; a slice that runs past the end; a layout mismatch.  PGPU_ERR_UNSUPPORTED: pools of more than one
+ * GPU, as for the aggregation calls.  All refusals are decided on the host before any launch or copy and leave *out
+ * untouched.  SIDE CHANNELS: these calls are not refused under pgpu_set_table_gather_policy(1) -- the address stream
+ * depends on the caller's plaintext indices only, as for upload and download. */
+#define PGPU_GATHER_ONE 0xFFFFFFFFFFFFFFFFull
+int pgpu_batch_gather(const pgpu_batch* const* xs, size_t n_src, const uint64_t* idx /* HOST, [n_out] */, size_t n_out,
+                      pgpu_batch** out);
+int pgpu_batch_concat(const pgpu_batch* const* xs, size_t n_src, pgpu_batch** out);
+int pgpu_batch_slice(const pgpu_batch* x, size_t start, size_t count, size_t step, pgpu_batch** out);
+/* The launch shape of a gather of n_out rows of row_bytes bytes (host-side query, needs no device; every output pointer may
+ * be NULL): lanes per row (a power of two, at most 16), rows per wavefront (64 / lanes, at least 4) and bytes per access
+ * (16 where row_bytes % 16 == 0, else 8).  Row sizes: 8 * pgpu_batch_words, or 4 * pgpu_batch_row_limbs for pair rows (304,
+ * 576, 896 bytes for 1024-, 2048-, 3072-bit keys).  PGPU_ERR_INVALID_PARAM: row_bytes == 0 or no multiple of 8, n_out == 0. */
+int pgpu_batch_gather_plan(size_t row_bytes, size_t n_out, int* lanes_per_row, int* rows_per_wavefront, int* vec_bytes);
+
 /* ---- instrumentation used by bench.py (roofline) ----
  * With timing enabled every kernel launch is bracketed by two HIP events recorded on the stream
  * the kernel is launched on (no synchronisation at launch time).  pgpu_timing_collect waits for
@@ -716,7 +758,9 @@ typedef enum pgpu_kernel_kind {
   PGPU_KERNEL_MATMUL = 11,    /* every launch of pgpu_batch_ct_matmul: per pass the table build, the multi-exponentiation, the fold */
   PGPU_KERNEL_BUCKET = 12,    /* every launch of pgpu_batch_ct_matvec_bucket: accumulation levels, bucket reductions, Horner */
   PGPU_KERNEL_CONV = 13,      /* every launch of pgpu_batch_ct_conv2d (and of _conv2d_signed but its inversion): per pass the table build, the multi-exponentiation, the fold */
-  PGPU_KERNEL_INVERT = 14     /* every launch of pgpu_batch_ct_negate / _sub: forward passes, walks back, the broadcast product */
+  PGPU_KERNEL_INVERT = 14,    /* every launch of pgpu_batch_ct_negate / _sub: forward passes, walks back, the broadcast product */
+  PGPU_KERNEL_GATHER = 15     /* row_gather_kernel: pgpu_batch_gather and the strided pgpu_batch_slice (form PGPU_FORM_FULL_WIDTH);
+                                 pgpu_batch_concat and the unit-step slice are copies and record nothing */
 } pgpu_kernel_kind;
 int pgpu_set_timing(int enabled);
 int pgpu_timing_collect(int* kinds, double* ms, int max_entries);

@@ -49,10 +49,13 @@ SYMBOLS = [
     "pgpu_batch_ct_matmul_signed", "pgpu_ct_matmul_signed_plan",
     "pgpu_batch_ct_conv2d_signed", "pgpu_ct_conv2d_signed_plan",
     "pgpu_batch_ct_spmv_signed", "pgpu_ct_spmv_signed_plan",
+    "pgpu_batch_gather", "pgpu_batch_concat", "pgpu_batch_slice", "pgpu_batch_gather_plan",
 ]
 FEATURE_4096_SPLIT = 1
 SEGMENT_NONE = 0xFFFFFFFF      # PGPU_SEGMENT_NONE: the element is left out of that group
 SCAN_REVERSE = 1               # PGPU_SCAN_REVERSE: suffix instead of prefix products
+GATHER_ONE = 0xFFFFFFFFFFFFFFFF   # PGPU_GATHER_ONE: the value 1 in the batch's domain (a ciphertext of 0)
+KERNEL_GATHER = 15             # PGPU_KERNEL_GATHER
 
 _lib = None
 
@@ -251,6 +254,14 @@ def lib():
     L.pgpu_batch_ct_spmv_signed.restype = c_int
     L.pgpu_ct_spmv_signed_plan.argtypes = L.pgpu_ct_spmv_plan.argtypes
     L.pgpu_ct_spmv_signed_plan.restype = c_int
+    L.pgpu_batch_gather.argtypes = [POINTER(c_void_p), c_size_t, c_void_p, c_size_t, POINTER(c_void_p)]
+    L.pgpu_batch_gather.restype = c_int
+    L.pgpu_batch_concat.argtypes = [POINTER(c_void_p), c_size_t, POINTER(c_void_p)]
+    L.pgpu_batch_concat.restype = c_int
+    L.pgpu_batch_slice.argtypes = [c_void_p, c_size_t, c_size_t, c_size_t, POINTER(c_void_p)]
+    L.pgpu_batch_slice.restype = c_int
+    L.pgpu_batch_gather_plan.argtypes = [c_size_t, c_size_t, POINTER(c_int), POINTER(c_int), POINTER(c_int)]
+    L.pgpu_batch_gather_plan.restype = c_int
     _lib = L
     return L
 

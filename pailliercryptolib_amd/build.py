@@ -61,7 +61,7 @@ def _objects():
     hip = [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + _switches() + inc
     host = ["g++", "-O2", "-std=c++17", "-fPIC", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"] + _switches() + inc
     kdeps = [os.path.join(CSRC, f) for f in ("kernels.hpp", "mont_core.hpp", "kargs.hpp", "launch.hpp")]
-    hdeps = [os.path.join(CSRC, f) for f in ("kargs.hpp", "launch.hpp", "runtime.hpp", "policy.hpp")]
+    hdeps = [os.path.join(CSRC, f) for f in ("kargs.hpp", "launch.hpp", "runtime.hpp", "policy.hpp", "gather.hpp")]
     hdeps += [os.path.join(ROOT, "include", "pgpu.h"), os.path.join(ROOT, "include", "ipcl", "bignum.h"),
               os.path.join(ROOT, "include", "ipcl", "utils", "serialize.hpp")]
     obj = os.path.join(HERE, "build")
@@ -71,7 +71,8 @@ def _objects():
         o = os.path.join(obj, f"k_modexp_{part}.o")
         out.append((o, hip + [f"-DPGPU_PART={part}", "-c", src, "-o", o], [src] + kdeps))
     src = os.path.join(CSRC, "k_misc.hip")
-    out.append((os.path.join(obj, "k_misc.o"), hip + ["-c", src, "-o", os.path.join(obj, "k_misc.o")], [src] + kdeps))
+    out.append((os.path.join(obj, "k_misc.o"), hip + ["-c", src, "-o", os.path.join(obj, "k_misc.o")],
+                [src, os.path.join(CSRC, "gather.hpp")] + kdeps))
     for part in hensel_parts():
         src = os.path.join(CSRC, "k_hensel.hip")
         o = os.path.join(obj, f"k_hensel_{part}.o")
@@ -114,7 +115,7 @@ def _objects():
     for name in ("capi.cpp", "policy.cpp", "runtime.cpp", os.path.join("host", "bignum.cpp")):
         src = os.path.join(CSRC, name)
         o = os.path.join(obj, os.path.basename(name).replace(".cpp", ".o"))
-        extra = [os.path.join(CSRC, f) for f in ("capi_keys.inc", "capi_batches.inc", "capi_aggregate.inc", "capi_timing.inc")] if name == "capi.cpp" else []
+        extra = [os.path.join(CSRC, f) for f in ("capi_keys.inc", "capi_batches.inc", "capi_aggregate.inc", "capi_index.inc", "capi_timing.inc")] if name == "capi.cpp" else []
         out.append((o, host + ["-c", src, "-o", o], [src] + hdeps + extra))
     return out
 

@@ -625,6 +625,7 @@ struct pgpu_pubkey {
     rt::Replicated full;     // the way back in Geo<2H,K>, R' = 2^(29*2*L2): n^2 | n*R' | n*R'*Rs | R'*Rs  (2*L2 limbs
                              // each; Rs = the radix of the n^2 context, which Montgomery-form batches carry)
     uint32_t n0inv = 0, n0inv_full = 0;
+    std::vector<uint32_t> one_host;   // the pair row of one (2 * L2 limbs) as `pub` holds it: what pgpu_batch_gather pads with
   };
   std::vector<std::shared_ptr<PubForm>> hforms;
   mutable std::vector<std::list<FbTable>> fbh;   // [device]: fixed-base tables of pairs (form hforms.back())
@@ -2743,6 +2744,7 @@ int pgpu_paillier_decrypt_crt(const pgpu_privkey* key, const uint64_t* c, uint64
 
 #include "capi_batches.inc"   // pgpu_batch_*: upload / download, encrypt / decrypt, element-wise operations, lanes
 #include "capi_aggregate.inc" // pgpu_batch_ct_matvec / _spmv / _weighted_sum / _segment_sum / _segment_scan / _pack, pgpu_ct_*_plan
+#include "capi_index.inc"     // pgpu_batch_gather / _concat / _slice, pgpu_batch_gather_plan
 
 // ---- diagnostics of the pool's self-checks and table budget ----
 int pgpu_replication_stats(uint64_t* images_verified, uint64_t* copies_repaired) {

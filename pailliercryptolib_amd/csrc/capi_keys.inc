@@ -52,6 +52,7 @@ int make_pub_form(const BigNumber& n, int n_words, int nsq_rbits, int H, int K, 
   to_limbs29((R % n) * BigNumber((Ipp32u)f->n0inv) % n, L2, h.data() + 2 * L2);
   const BigNumber Rm = R % P2, R2 = (Rm * Rm) % P2;
   put_pair(h.data() + 3 * L2, Rm);
+  f->one_host.assign(h.begin() + 3 * L2, h.begin() + 5 * L2);
   // (second set: bases that arrive as c*Rs mod n^2 -- resident ciphertexts)
   const BigNumber Rs = pow2(nsq_rbits);
   const BigNumber R2m = (R2 * P2.InverseMul(Rs % P2)) % P2;

@@ -100,6 +100,21 @@ CipherText CipherText::getCipherText(const size_t& idx) const {
 std::shared_ptr<PublicKey> CipherText::getPubKey() const { return m_pk; }
 
 CipherText CipherText::rotate(int shift) const {
+  dropStaleDevice();
+  // (pools of more than one GPU: pgpu_batch_gather does not shard rows yet, so such a text takes the host path below, as
+  // every text did before)
+  if (isDeviceResident() && pgpu_pool_size() == 1) {
+    // the current copy is the device's: rotated there, the result stays resident (the checks and messages of
+    // detail::rotated; positive shift moves elements towards higher indices)
+    const int size = (int)m_size;
+    ERROR_CHECK(size != 1, "rotate: Cannot rotate single CipherText");
+    ERROR_CHECK(shift >= -size && shift <= size, "rotate: Cannot shift more than the test size");
+    if (shift == 0 || shift == size || shift == -size) return *this;
+    const std::size_t left = (std::size_t)(shift > 0 ? size - shift : -shift);
+    std::vector<uint64_t> idx(m_size);
+    for (std::size_t i = 0; i < m_size; ++i) idx[i] = (i + left) % m_size;
+    return indexMap("rotate", {this}, &idx, 0, 0, 0);
+  }
   ensureHost();
   return CipherText(*m_pk, detail::rotated(m_texts, shift));
 }

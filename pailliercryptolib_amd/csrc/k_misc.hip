@@ -1,6 +1,8 @@
-// pailliercryptolib_amd -- instantiations of the modmul / crt / fixed-base kernels for every throughput geometry.
+// pailliercryptolib_amd -- instantiations of the modmul / crt / fixed-base kernels for every throughput geometry,
+// and of the row gather (gather.hpp).
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "gather.hpp"
 
 namespace pgpu {
 
@@ -48,6 +50,13 @@ bool launch_fb_build(int G, int K, const FixedBaseBuildArgs& a, unsigned blocks,
 bool launch_fb_encrypt(int G, int K, const FixedBaseArgs& a, unsigned blocks, hipStream_t s) {
   PGPU_FOR_GEOS(PGPU_ONE_FBE)
   return false;
+}
+// re-indexing of resident batches (gather.hpp): pieces of 16 bytes where the rows allow them, of 8 otherwise
+bool launch_row_gather(int vec_bytes, const GatherArgs& a, unsigned blocks, hipStream_t s) {
+  if (vec_bytes == 16) hipLaunchKernelGGL((row_gather_kernel<gather_piece16>), dim3(blocks), dim3(kWGThreads), 0, s, a);
+  else if (vec_bytes == 8) hipLaunchKernelGGL((row_gather_kernel<gather_piece8>), dim3(blocks), dim3(kWGThreads), 0, s, a);
+  else return false;
+  return true;
 }
 
 }  // namespace pgpu

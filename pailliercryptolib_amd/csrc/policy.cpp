@@ -1032,5 +1032,58 @@ void wsum_image(const std::vector<const uint32_t*>& tab, const std::vector<const
   out->fold_steps_at = out->image.add(fold.steps);
 }
 
+// ---- gather, concat and slice of resident batches ----
+bool gather_plan(size_t row_bytes, size_t n_out, GatherPlan* plan) {
+  if (row_bytes == 0 || row_bytes % 8 != 0 || row_bytes > 0xFFFFFFFFull || n_out == 0) return false;
+  GatherPlan p;
+  p.vec_bytes = row_bytes % 16 == 0 ? 16 : 8;
+  const size_t pieces = row_bytes / (size_t)p.vec_bytes;
+  while ((1u << p.lanes_log2) < kGatherMaxLanes && ((size_t)1 << p.lanes_log2) < pieces) ++p.lanes_log2;
+  p.lanes_per_row = 1 << p.lanes_log2;
+  p.rows_per_wavefront = kWave / p.lanes_per_row;
+  p.wavefronts = (n_out + (size_t)p.rows_per_wavefront - 1) / (size_t)p.rows_per_wavefront;
+  p.blocks = (p.wavefronts + kWavesPerWG - 1) / kWavesPerWG;
+  *plan = p;
+  return true;
+}
+
+size_t gather_counts_ok(const size_t* counts, size_t n_src) {
+  for (size_t k = 0; k < n_src; ++k)
+    if (counts[k] >= kGatherMaxRows) return k;
+  return n_src;
+}
+
+size_t gather_descs(const size_t* counts, size_t n_src, const uint64_t* idx, size_t n_out, std::vector<GatherDesc>* desc) {
+  std::vector<uint64_t> end(n_src);   // end[k]: rows of sources 0..k
+  uint64_t total = 0;
+  for (size_t k = 0; k < n_src; ++k) end[k] = total += counts[k];
+  desc->resize(n_out);
+  size_t k = 0;                       // (the source of the previous index: neighbouring indices mostly share it)
+  for (size_t i = 0; i < n_out; ++i) {
+    const uint64_t v = idx[i];
+    if (v == kGatherOne) {
+      (*desc)[i] = GatherDesc{0u, kGatherOneRow};
+      continue;
+    }
+    if (v >= total) return i;
+    if (v >= end[k] || (k && v < end[k - 1])) k = (size_t)(std::upper_bound(end.begin(), end.end(), v) - end.begin());
+    (*desc)[i] = GatherDesc{(uint32_t)k, (uint32_t)(v - (k ? end[k - 1] : 0))};
+  }
+  return n_out;
+}
+
+void gather_slice_descs(size_t start, size_t count, size_t step, std::vector<GatherDesc>* desc) {
+  desc->resize(count);
+  for (size_t i = 0; i < count; ++i) (*desc)[i] = GatherDesc{0u, (uint32_t)(start + i * step)};
+}
+
+void gather_image(const std::vector<const char*>& bases, const void* one, size_t row_bytes, const std::vector<GatherDesc>& desc,
+                  GatherImage* out) {
+  *out = GatherImage();
+  out->bases_at = out->image.add(bases);
+  out->one_at = out->image.add(one, row_bytes, 16);
+  out->desc_at = out->image.add(desc, 8);
+}
+
 }  // namespace policy
 }  // namespace pgpu

@@ -19,6 +19,7 @@
 #include <utility>
 #include <vector>
 
+#include "gather.hpp"
 #include "kargs.hpp"
 
 namespace pgpu {
@@ -607,6 +608,39 @@ struct WsumImage {
 };
 void wsum_image(const std::vector<const uint32_t*>& tab, const std::vector<const uint32_t*>& ftab, const WsumPlan& plan,
                 const WsumPlan& fold, WsumImage* out);
+
+
+// ---- gather, concat and slice of resident batches (gather.hpp; pgpu_batch_gather / _concat / _slice,
+//      pgpu_batch_gather_plan) ----
+// Rows move as bytes.  1. the launch shape, from the row size alone: pieces of 16 bytes where row_bytes % 16 == 0, of 8
+//    otherwise; a row is swept by the smallest power of two of lanes that covers its pieces, at most kGatherMaxLanes = 16
+//    -- so a wavefront holds 64 / lanes >= 4 rows, each lane up to kGatherUnroll loads ahead of its stores: the recipe
+//    measured for gathered whole rows (4 rows in flight per wavefront), never one lane per multi-piece row.  Rows of 8
+//    bytes are one piece: one lane each, 64 neighbouring outputs per wavefront.
+//    false: row_bytes == 0 or no multiple of 8, or n_out == 0 (nothing is written then).
+constexpr uint64_t kGatherOne = ~(uint64_t)0;       // index sentinel: the row of one
+constexpr size_t kGatherMaxSources = 65535;
+constexpr size_t kGatherMaxRows = 0xFFFFFFFFull;    // a source holds FEWER rows than this (row numbers are 32 bits, all ones is the sentinel)
+// the first source that holds kGatherMaxRows rows or more (the call is refused then), or n_src: every count is addressable
+size_t gather_counts_ok(const size_t* counts, size_t n_src);
+struct GatherPlan {
+  int vec_bytes = 0, lanes_per_row = 0, rows_per_wavefront = 0, lanes_log2 = 0;
+  size_t wavefronts = 0, blocks = 0;
+};
+bool gather_plan(size_t row_bytes, size_t n_out, GatherPlan* plan);
+// 2. the descriptors: flat index i of the concatenation of sources of counts[0..n_src) rows -> (source, row); kGatherOne ->
+//    (0, kGatherOneRow).  A handle named twice is two sources to this function.  Returns n_out, or the FIRST position whose
+//    index is at or beyond the total count and not the sentinel (desc is unspecified then).
+size_t gather_descs(const size_t* counts, size_t n_src, const uint64_t* idx, size_t n_out, std::vector<GatherDesc>* desc);
+//    ... and of the strided slice: rows start, start + step, ... of source 0
+void gather_slice_descs(size_t start, size_t count, size_t step, std::vector<GatherDesc>* desc);
+// 3. the image: the source bases (8-byte entries), the row of one at a 16-byte boundary, the descriptors
+struct GatherImage {
+  PlanImage image;
+  size_t bases_at = 0, one_at = 0, desc_at = 0;
+};
+void gather_image(const std::vector<const char*>& bases, const void* one, size_t row_bytes, const std::vector<GatherDesc>& desc,
+                  GatherImage* out);
 
 }  // namespace policy
 }  // namespace pgpu

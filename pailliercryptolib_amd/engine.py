@@ -368,6 +368,36 @@ class PublicKey:
                                                                 _ptr(wa) if wa is not None else None,
                                                                 wa.shape[1] if wa is not None else 0, out))
 
+    @staticmethod
+    def _sources(h):
+        """the uploaded handles of a _resident_call as the `const pgpu_batch* const*` array of a several-source call"""
+        return (ctypes.c_void_p * len(h))(*[v.value for v in h])
+
+    def gather(self, x, idx):
+        """Re-indexing on the device: x a list of ciphertexts (ints modulo n^2), or a list of such lists (the sources, put
+        end to end), idx a list of positions in any order, repeats allowed; None is the ciphertext 1 (an encryption of 0:
+        padding, a missing value) -> the list [x[i] for i in idx].  One pgpu_batch_gather call on resident batches (rows
+        move as bytes, one launch); there is no host indexing behind it."""
+        xs = [list(r) for r in x] if len(x) and isinstance(x[0], (list, tuple)) else [list(x)]
+        total = sum(len(r) for r in xs)
+        if total == 0 or any(len(r) == 0 for r in xs) or len(idx) == 0:
+            raise RuntimeError("gather error: empty batch or empty index list")
+        flat = [_capi.GATHER_ONE if v is None else int(v) for v in idx]
+        if any(v < 0 or (v >= total and v != _capi.GATHER_ONE) for v in flat):
+            raise RuntimeError("gather error: an index is not below the number of rows")
+        ia = np.array(flat, dtype=np.uint64)
+        return self._resident_call([self._ct(r) for r in xs], len(flat), lambda L, h, out:
+                                   L.pgpu_batch_gather(self._sources(h), len(h), _ptr(ia), len(flat), out))
+
+    def concat(self, xs):
+        """xs a list of lists of ciphertexts (ints modulo n^2) -> the one list that holds them end to end, put together
+        on the device: one pgpu_batch_concat call on resident batches (one device-to-device copy per source)."""
+        xs = [list(r) for r in xs]
+        if len(xs) == 0 or any(len(r) == 0 for r in xs):
+            raise RuntimeError("concat error: empty batch")
+        return self._resident_call([self._ct(r) for r in xs], sum(len(r) for r in xs), lambda L, h, out:
+                                   L.pgpu_batch_concat(self._sources(h), len(h), out))
+
     def segment_sum(self, x, ids, n_segments):
         """Encrypted segmented sum: x a list of ciphertexts (ints modulo n^2), ids one flat list of segment numbers (one
         group) or a list of such lists (several groupings of the same x); None leaves an element out of that group ->
