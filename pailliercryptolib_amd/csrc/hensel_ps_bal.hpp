@@ -43,6 +43,21 @@
 #ifndef PGPU_PSB_KARATSUBA
 #define PGPU_PSB_KARATSUBA 1
 #endif
+// 1 (default): the upper half of a reduction is folded the same way.  From column K on every quotient digit is known, and the
+// q * n terms of columns K .. 2K-2 are the upper part of a plain product of two known operands, q = q0 + q1 B^18 and
+// n = n0 + n1 B^18: its cross terms q0 n1 + q1 n0 of index k = 18 .. 34 (column k + 18) are L'_k + H'_k + M'_k with L' = q0 n0,
+// H' = q1 n1, M' = (q0 - q1)(n1 - n0).  L'_k is the sum the digit-serial column k formed anyway, H'_k the sum column k + 36
+// needs anyway: both wait in a chain, and the 2 x 153 cross products become the 153 of M' -- 1143 q * n products per reduction
+// instead of 1296, for 18 subtractions (dq = q0 - q1; dn = n1 - n0 is wave-uniform, formed once per kernel).  Where the operand
+// product is in the Karatsuba form already (a2 * b, a * c) the terms ride on its chains and joins (L'_k in L_k, H'_k in Hh_k:
+// the same columns), with no new waiting value and no new join.  The same column sums in another order, the same digits and
+// limbs bit for bit.  The symmetric product's reduction (chains of its own: measured, no gain in the headline,
+// profiles/ps_kara_reduction.txt), the two-product scan, the entry and the exit keep the schoolbook reduction.  0: the
+// schoolbook reduction everywhere, the parent's code instruction for instruction (A/B: tools/ubench_ps.hip has both forms as
+// template arguments).  Takes effect with PGPU_PSB_KARATSUBA.  Model: tests/test_ps_kara_reduction_model.py.
+#ifndef PGPU_PSB_KARA_RED
+#define PGPU_PSB_KARA_RED 1
+#endif
 
 namespace pgpu {
 
@@ -78,13 +93,17 @@ struct PsbFits {
 // accumulator: a column is at most 18 products of 2^(2LB-1), one square and K q*n terms -- 73 * 2^56 at K = 36, LB = 29.
 // KARA (single product, not SYM, K even): the operand products in the Karatsuba form, |x1 limb| <= 2^LB, |y1 limb| <= 2^(LB-1):
 // the differences of the halves fit int32_t (2^(LB+1), 2^LB), a half product's column sum is at most 18 * 2^(2LB-1) < 2^63.
-template <int K, int LB, int NP, bool SYM, int QMODE, bool DBL = false, bool KARA = false>
+// KRED (with KARA): the q * n terms of columns K .. 2K-2 in the folded form (PGPU_PSB_KARA_RED), dn[j] = n[H + j] - n[j]
+// (wave-uniform, |dn| < 2^LB); dq = q0 - q1 is at most 2^LB.  A chain that waits then holds at most 17 operand products of
+// 2^(2LB-1) and 17 q * n terms of 2^(2LB-2), and everything about it is wrapping arithmetic.  Without KRED dn is not read.
+template <int K, int LB, int NP, bool SYM, int QMODE, bool DBL = false, bool KARA = false, bool KRED = false>
 __device__ __forceinline__ void psb_montmul(int32_t (&r)[K], const int32_t (&x1)[K], const int32_t (&y1)[K],
                                             const int32_t (&x2)[K], const int32_t (&y2)[K], const int32_t (&n)[K],
-                                            uint32_t n0inv, int32_t (&qio)[K]) {
+                                            const int32_t (&dn)[K / 2], uint32_t n0inv, int32_t (&qio)[K]) {
   static_assert(!(SYM && NP != 1), "a symmetric product is a single one");
   static_assert(SYM || !DBL, "the doubled operand belongs to the symmetric product");
   static_assert(!KARA || (NP == 1 && !SYM && K % 2 == 0), "the split serves the single product of two operands, in two halves");
+  static_assert(!KRED || KARA, "the folded reduction rides on the chains of the split product");
   static_assert(PsbFits<K, LB>::value, "a column sums up to 3K products below 2^(2(LB-1)): must stay below 2^63");
   constexpr int H = K / 2;
   int32_t q[K];
@@ -94,6 +113,8 @@ __device__ __forceinline__ void psb_montmul(int32_t (&r)[K], const int32_t (&x1)
   // KARA: the differences of the halves, and the column sums of the low and the high half products while they wait
   int32_t dx[KARA ? H : 1], dy[KARA ? H : 1];
   uint64_t lo[KARA ? 2 * H - 1 : 1], hi[KARA ? 2 * H - 1 : 1];
+  // KRED: q0 - q1 (formed at column K, when q is complete)
+  int32_t dq[KRED ? H : 1];
   if constexpr (KARA) {
 #pragma unroll
     for (int j = 0; j < H; ++j) {
@@ -104,7 +125,7 @@ __device__ __forceinline__ void psb_montmul(int32_t (&r)[K], const int32_t (&x1)
   ps_static_for<2 * K>([&](auto colc) __attribute__((always_inline)) {
     constexpr int col = decltype(colc)::value;
     // ---- q_i * n_j of the digits found so far, j >= 1 (n_0 belongs to the digit step), onto the carry of the column below
-    {
+    if constexpr (!KRED) {
       constexpr int ilo = col < K ? 0 : col - K + 1;
       constexpr int ihi = col < K ? col : K;               // i <= col - 1
       if constexpr (ihi > ilo) {
@@ -112,6 +133,31 @@ __device__ __forceinline__ void psb_montmul(int32_t (&r)[K], const int32_t (&x1)
           constexpr int i = ilo + decltype(ic)::value;
           if constexpr (PGPU_PS_PIN == 2 || (PGPU_PS_PIN == 1 && SYM)) psb_mac_pinned(acc, q[i], n[col - i]);
           else psb_mac(acc, q[i], n[col - i]);
+        });
+      }
+    } else {
+      // the folded form.  Below K: the q0 * n0 terms of columns H .. K-1 (i and col - i both below H) go into the chain that
+      // waits as L'_col (with the operand products, below), every other term straight onto the accumulator, the newest
+      // digit last.  From K on: only the q1 * n1 terms of index col - K < H; those of index H .. 2H-2 are H', the cross
+      // terms L' + H' + M' (both with the operand products, below)
+      if constexpr (col == K) {
+#pragma unroll
+        for (int j = 0; j < H; ++j) dq[j] = q[j] - q[H + j];
+      }
+      if constexpr (col > 0 && col < K) {
+        ps_static_for<col>([&](auto ic) __attribute__((always_inline)) {
+          constexpr int i = decltype(ic)::value;
+          if constexpr (!(col >= H && i < H && col - i < H)) {
+            if constexpr (PGPU_PS_PIN == 2 || (PGPU_PS_PIN == 1 && SYM)) psb_mac_pinned(acc, q[i], n[col - i]);
+            else psb_mac(acc, q[i], n[col - i]);
+          }
+        });
+      } else if constexpr (col >= K && col < K + H) {
+        constexpr int m = col - K;
+        ps_static_for<m + 1>([&](auto ic) __attribute__((always_inline)) {
+          constexpr int i = decltype(ic)::value;
+          if constexpr (PGPU_PS_PIN == 2 || (PGPU_PS_PIN == 1 && SYM)) psb_mac_pinned(acc, q[H + i], n[H + m - i]);
+          else psb_mac(acc, q[H + i], n[H + m - i]);
         });
       }
     }
@@ -152,6 +198,12 @@ __device__ __forceinline__ void psb_montmul(int32_t (&r)[K], const int32_t (&x1)
           constexpr int i = ilo + decltype(ic)::value;
           psb_mac_wrap(s, x1[i], y1[col - i]);
         });
+        if constexpr (KRED && col >= H) {                  // L'_col: the q0 * n0 terms of this column, the same i
+          ps_static_for<ihi - ilo>([&](auto ic) __attribute__((always_inline)) {
+            constexpr int i = ilo + decltype(ic)::value;
+            psb_mac_wrap(s, q[i], n[col - i]);
+          });
+        }
         lo[col] = (uint64_t)s;
         acc = (int64_t)((uint64_t)acc + lo[col]);
       }
@@ -164,12 +216,24 @@ __device__ __forceinline__ void psb_montmul(int32_t (&r)[K], const int32_t (&x1)
           constexpr int i = ilo + decltype(ic)::value;
           psb_mac_wrap(s, x1[H + i], y1[H + k - i]);
         });
+        if constexpr (KRED && k >= H) {                    // H'_k: the q1 * n1 terms column k + 2H would take
+          ps_static_for<ihi - ilo>([&](auto ic) __attribute__((always_inline)) {
+            constexpr int i = ilo + decltype(ic)::value;
+            psb_mac_wrap(s, q[H + i], n[H + k - i]);
+          });
+        }
         hi[k] = (uint64_t)s;
         acc = (int64_t)((uint64_t)acc + (lo[k] + hi[k]));
         ps_static_for<ihi - ilo>([&](auto ic) __attribute__((always_inline)) {
           constexpr int i = ilo + decltype(ic)::value;
           psb_mac_wrap(acc, dx[i], dy[k - i]);
         });
+        if constexpr (KRED && k >= H) {                    // M'_k
+          ps_static_for<ihi - ilo>([&](auto ic) __attribute__((always_inline)) {
+            constexpr int i = ilo + decltype(ic)::value;
+            psb_mac_wrap(acc, dq[i], dn[k - i]);
+          });
+        }
       }
       if constexpr (col >= 2 * H && col <= 4 * H - 2) acc = (int64_t)((uint64_t)acc + hi[col - 2 * H]);
     } else {
@@ -209,20 +273,24 @@ __device__ __forceinline__ const uint32_t (&psb_bits(const int32_t (&v)[K]))[K] 
 // DBL: a2 = 2a serves both products (|2a| <= 2^LB as well): t = sym(a2, a), b = (a2*b + q) reduced -- the same column sums in
 // another order of summation, so the same digits and the same limbs, bit for bit.
 // KARA (with DBL): the b part's a2 * b in the Karatsuba form of psb_montmul.
-template <int K, int LB, bool DBL = (PGPU_PSB_DOUBLED != 0), bool KARA = (PGPU_PSB_KARATSUBA != 0)>
-__device__ __forceinline__ void psb_pairsqr(int32_t (&a)[K], int32_t (&b)[K], const int32_t (&n)[K], uint32_t n0inv) {
+// KRED (with DBL and KARA): the b part's reduction folded onto the chains of a2 * b.
+template <int K, int LB, bool DBL = (PGPU_PSB_DOUBLED != 0), bool KARA = (PGPU_PSB_KARATSUBA != 0),
+          bool KRED = (DBL && KARA && PGPU_PSB_KARA_RED != 0)>
+__device__ __forceinline__ void psb_pairsqr(int32_t (&a)[K], int32_t (&b)[K], const int32_t (&n)[K], const int32_t (&dn)[K / 2],
+                                            uint32_t n0inv) {
+  static_assert(!KRED || (DBL && KARA), "the folded reduction belongs to the doubled Karatsuba form");
   int32_t qd[K], t[K];
   if constexpr (DBL) {
     int32_t a2[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) a2[j] = a[j] * 2;
-    psb_montmul<K, LB, 1, true, 1, true>(t, a2, a, a2, a, n, n0inv, qd);
-    psb_montmul<K, LB, 1, false, 2, false, KARA>(b, a2, b, a2, b, n, n0inv, qd);
+    psb_montmul<K, LB, 1, true, 1, true>(t, a2, a, a2, a, n, dn, n0inv, qd);
+    psb_montmul<K, LB, 1, false, 2, false, KARA, KRED>(b, a2, b, a2, b, n, dn, n0inv, qd);
   } else {
-    psb_montmul<K, LB, 1, true, 1>(t, a, a, a, a, n, n0inv, qd);
+    psb_montmul<K, LB, 1, true, 1>(t, a, a, a, a, n, dn, n0inv, qd);
 #pragma unroll
     for (int j = 0; j < K; ++j) b[j] *= 2;
-    psb_montmul<K, LB, 1, false, 2>(b, a, b, a, b, n, n0inv, qd);
+    psb_montmul<K, LB, 1, false, 2>(b, a, b, a, b, n, dn, n0inv, qd);
   }
 #pragma unroll
   for (int j = 0; j < K; ++j) a[j] = t[j];
@@ -231,20 +299,21 @@ __device__ __forceinline__ void psb_pairsqr(int32_t (&a)[K], int32_t (&b)[K], co
 // (a, b) = (a, b) (x) (c, d) (ps_pairmul: b waits in LDS through the first product, t through the second)
 // KARA: the first product a * c in the Karatsuba form (balanced operands: the window loop and the table build; the entry and
 // the exit, whose limbs are relaxed sums and which run once, pass false)
-template <int K, int LB, bool KARA = (PGPU_PSB_KARATSUBA != 0)>
+// KRED (with KARA): the first product's reduction folded onto its chains; the two-product scan keeps the schoolbook reduction
+template <int K, int LB, bool KARA = (PGPU_PSB_KARATSUBA != 0), bool KRED = (KARA && PGPU_PSB_KARA_RED != 0)>
 __device__ __forceinline__ void psb_pairmul(int32_t (&a)[K], int32_t (&b)[K], const int32_t (&c)[K], const int32_t (&d)[K],
-                                            const int32_t (&n)[K], uint32_t n0inv, uint4* slot) {
+                                            const int32_t (&n)[K], const int32_t (&dn)[K / 2], uint32_t n0inv, uint4* slot) {
   int32_t qd[K];
   {
     int32_t t[K];
     ps_park_store<K>(slot, psb_bits<K>(b));
     __builtin_amdgcn_sched_barrier(0);
-    psb_montmul<K, LB, 1, false, 1, false, KARA>(t, a, c, a, c, n, n0inv, qd);
+    psb_montmul<K, LB, 1, false, 1, false, KARA, KRED>(t, a, c, a, c, n, dn, n0inv, qd);
     __builtin_amdgcn_sched_barrier(0);
     ps_park_swap<K>(slot, psb_bits<K>(b), psb_bits<K>(t));
     __builtin_amdgcn_sched_barrier(0);
   }
-  psb_montmul<K, LB, 2, false, 2>(b, a, d, b, c, n, n0inv, qd);
+  psb_montmul<K, LB, 2, false, 2>(b, a, d, b, c, n, dn, n0inv, qd);
   __builtin_amdgcn_sched_barrier(0);
   ps_park_load<K>(psb_bits<K>(a), slot);
 }
@@ -253,8 +322,8 @@ __device__ __forceinline__ void psb_pairmul(int32_t (&a)[K], int32_t (&b)[K], co
 template <int K, int LB>
 __device__ __forceinline__ void psb_mul(int32_t (&r)[K], const int32_t (&x)[K], const int32_t (&y)[K], const int32_t (&n)[K],
                                         uint32_t n0inv) {
-  int32_t none[K];
-  psb_montmul<K, LB, 1, false, 0>(r, x, y, x, y, n, n0inv, none);
+  int32_t none[K], nodn[K / 2] = {};
+  psb_montmul<K, LB, 1, false, 0>(r, x, y, x, y, n, nodn, n0inv, none);
 }
 
 // a += k with a carry round that re-balances (limbs may be sums of a few balanced limbs); the value must fit K balanced limbs
@@ -308,7 +377,7 @@ __device__ __forceinline__ void psb_entry_from_pair_row(const HenselArgs& A, int
   constexpr int NI = (K * LB - 2) / LB + 1;      // row limbs per entry chunk that fit a half, plus one for the carry
 #define HCTX(field) (side ? A.ctx[1].field : A.ctx[0].field)
   const uint32_t* row = A.ct_pair + elem * A.ct_pair_stride;
-  int32_t acc_a[K], acc_b[K];
+  int32_t acc_a[K], acc_b[K], nodn[K / 2] = {};      // (nodn: the schoolbook reduction reads no differences)
 #pragma unroll
   for (int j = 0; j < K; ++j) acc_a[j] = acc_b[j] = 0;
 #pragma unroll 1
@@ -333,7 +402,7 @@ __device__ __forceinline__ void psb_entry_from_pair_row(const HenselArgs& A, int
     psb_relimb<K, LB, NI>(zl, zb);
     psb_mul<K, LB>(tb, zl, cb, n, n0inv);
     psb_relimb<K, LB, NI>(a, za);
-    psb_pairmul<K, LB, false>(a, b, ma, mb, n, n0inv, slot);
+    psb_pairmul<K, LB, false>(a, b, ma, mb, n, nodn, n0inv, slot);
     psb_add<K, LB>(b, tb);
     psb_add<K, LB>(acc_a, a);
     psb_add<K, LB>(acc_b, b);
@@ -361,7 +430,8 @@ __device__ __forceinline__ void psb_exit_words(const HenselArgs& A, int side, si
     ma[j] = (int32_t)HCTX(h)[j];
     mb[j] = 0;
   }
-  psb_pairmul<K, LB, false>(a, b, ma, mb, n, n0inv, slot);
+  int32_t nodn[K / 2] = {};
+  psb_pairmul<K, LB, false>(a, b, ma, mb, n, nodn, n0inv, slot);
   uint32_t u0[K], u1[K];
   const int32_t neg_a = psb_canon<K, LB>(u0, a);             // -1: a' < 0
 #pragma unroll
@@ -409,6 +479,10 @@ __global__ __launch_bounds__(kWGThreads, MINW) void hensel_decrypt_psb_kernel(He
 #pragma unroll
   for (int j = 0; j < K; ++j) n[j] = (int32_t)ps_uniform(HCTX(nhat)[j]);   // wave-uniform: SGPR operands of the products
   const uint32_t n0inv = ps_uniform(HCTX(n0inv));
+  // n1 - n0 of the folded reductions (PGPU_PSB_KARA_RED), wave-uniform like n
+  int32_t dn[K / 2];
+#pragma unroll
+  for (int j = 0; j < K / 2; ++j) dn[j] = PGPU_PSB_KARA_RED != 0 ? (int32_t)ps_uniform((uint32_t)(n[K / 2 + j] - n[j])) : 0;
   const int w = A.window, tsize = 1 << w, half = tsize >> 1;
   const bool gather = A.ct_gather != 0;
   // the odd-power table and the product placed inside the window (hensel_ps.hpp); the masked policy keeps the full table and
@@ -447,13 +521,13 @@ __global__ __launch_bounds__(kWGThreads, MINW) void hensel_decrypt_psb_kernel(He
     const bool sq = !odd || k == 0, mu = !odd || k > 0;
     ps_table_load<K>(psb_bits<K>(a), psb_bits<K>(b), tw, k > 1 ? k : 1, tsize, false);
     if (sq) {
-      psb_pairsqr<K, LB>(a, b, n, n0inv);
+      psb_pairsqr<K, LB>(a, b, n, dn, n0inv);
       ps_table_store<K>(tw, odd ? half : 2 * k, psb_bits<K>(a), psb_bits<K>(b));
     }
     __builtin_amdgcn_sched_barrier(0);      // (the multiplier is fetched AFTER the squaring: held across it, it costs 2K registers)
     if (mu) {
       ps_table_load<K>(psb_bits<K>(ma), psb_bits<K>(mb), tw, odd ? half : 1, tsize, false);
-      psb_pairmul<K, LB>(a, b, ma, mb, n, n0inv, slot);
+      psb_pairmul<K, LB>(a, b, ma, mb, n, dn, n0inv, slot);
       ps_table_store<K>(tw, odd ? k + 1 : 2 * k + 1, psb_bits<K>(a), psb_bits<K>(b));
     }
   }
@@ -481,9 +555,9 @@ __global__ __launch_bounds__(kWGThreads, MINW) void hensel_decrypt_psb_kernel(He
       if (i == pos) {
         // (the entry is fetched where it is used: held across squarings it would cost 2K registers)
         ps_table_load<K>(psb_bits<K>(ma), psb_bits<K>(mb), tw, idx, tsize, gather);
-        psb_pairmul<K, LB>(a, b, ma, mb, n, n0inv, slot);
+        psb_pairmul<K, LB>(a, b, ma, mb, n, dn, n0inv, slot);
       }
-      if (i < wl) psb_pairsqr<K, LB>(a, b, n, n0inv);
+      if (i < wl) psb_pairsqr<K, LB>(a, b, n, dn, n0inv);
     }
   }
   // ---- exit under the prime: (a, b) times (hp, 0);  mp = ([a' >= p] - [a' < 0] - b') mod p ----

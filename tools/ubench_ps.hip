@@ -16,6 +16,8 @@
 // hensel_decrypt_psb_kernel (one body of each operation, wave-uniform branches).
 // Fifth part (the Karatsuba split of the single products): exp_kernel_bal<..., KARA = true> runs psb_pairsqr / psb_pairmul with the
 // a2*b and a*c products split in the middle next to the schoolbook form, the odd-table loop shape, the parent's form first and last.
+// Sixth part (the folded reductions, hensel_ps_bal.hpp KRED): exp_kernel_bal<..., KRED = true> folds the upper q*n columns of the
+// reductions of a2*b and a*c, next to the parent's form (KARA alone) in the same binary; `ubench_ps r` runs this part alone.
 // Reported in shader cycles per exponentiation (no instruction count needed).
 // build: python tools/build_ubench.py ubench_ps -I<repo>/pailliercryptolib_amd/csrc [-DPGPU_PS_SPLIT=1]   (the library's compile step, alignment pass included)
 #include <hip/hip_runtime.h>
@@ -82,17 +84,20 @@ __global__ __launch_bounds__(256, MINW) void sq_kernel_bal(const uint32_t* in, c
     n[j] = (int32_t)ps_uniform(nn[j]);
   }
   const uint32_t n0inv = ps_uniform(n0inv_in);
+  int32_t dn[K / 2];
+#pragma unroll
+  for (int j = 0; j < K / 2; ++j) dn[j] = (int32_t)ps_uniform((uint32_t)(n[K / 2 + j] - n[j]));
   const unsigned long long t0 = __builtin_readcyclecounter();
 #pragma unroll 1
   for (int w = 0; w < iters; ++w) {
 #pragma unroll 1
-    for (int i = 0; i < 5; ++i) psb_pairsqr<K, LB>(a, b, n, n0inv);
+    for (int i = 0; i < 5; ++i) psb_pairsqr<K, LB>(a, b, n, dn, n0inv);
 #pragma unroll
     for (int j = 0; j < K; ++j) {
       c[j] = (int32_t)(in[(size_t)lane * 2 * K + j] ^ (w & 1));
       d[j] = (int32_t)(in[(size_t)lane * 2 * K + K + j] ^ (w & 2));
     }
-    psb_pairmul<K, LB>(a, b, c, d, n, n0inv, slot);
+    psb_pairmul<K, LB>(a, b, c, d, n, dn, n0inv, slot);
   }
   const unsigned long long t1 = __builtin_readcyclecounter();
   if (threadIdx.x % kWave == 0) cyc[lane / kWave] = t1 - t0;
@@ -104,8 +109,8 @@ __global__ __launch_bounds__(256, MINW) void sq_kernel_bal(const uint32_t* in, c
 }
 
 // one exponentiation's operations on balanced limbs: `build` times ([a squaring if half] + a product), then `nwin` times
-// (w squarings + [a product if do_mul]); DBL: the pair squaring on the doubled operand
-template <int K, int LB, int MINW, bool DBL, bool ODD = false, bool KARA = false>
+// (w squarings + [a product if do_mul]); DBL: the pair squaring on the doubled operand; KRED: the reductions of a2*b and a*c folded
+template <int K, int LB, int MINW, bool DBL, bool ODD = false, bool KARA = false, bool KRED = false>
 __global__ __launch_bounds__(256, MINW) void exp_kernel_bal(const uint32_t* in, const uint32_t* nn, uint32_t* out,
                                                             unsigned long long* cyc, uint32_t n0inv_in, int build, int half,
                                                             int nwin, int w, int do_mul) {
@@ -122,12 +127,15 @@ __global__ __launch_bounds__(256, MINW) void exp_kernel_bal(const uint32_t* in, 
     n[j] = (int32_t)ps_uniform(nn[j]);
   }
   const uint32_t n0inv = ps_uniform(n0inv_in);
+  int32_t dn[K / 2];
+#pragma unroll
+  for (int j = 0; j < K / 2; ++j) dn[j] = KRED ? (int32_t)ps_uniform((uint32_t)(n[K / 2 + j] - n[j])) : 0;
   const unsigned long long t0 = __builtin_readcyclecounter();
   if constexpr (ODD) {
     // `half` holds the squarings of the top window here.  Table: trip 0 squares, trips 1 .. build multiply
 #pragma unroll 1
     for (int e = 0; e <= build; ++e) {
-      if (e == 0) psb_pairsqr<K, LB, DBL, KARA>(a, b, n, n0inv);
+      if (e == 0) psb_pairsqr<K, LB, DBL, KARA, KRED>(a, b, n, dn, n0inv);
       __builtin_amdgcn_sched_barrier(0);
       if (e > 0) {
 #pragma unroll
@@ -135,7 +143,7 @@ __global__ __launch_bounds__(256, MINW) void exp_kernel_bal(const uint32_t* in, 
           c[j] = (int32_t)(in[(size_t)lane * 2 * K + j] ^ (e & 1));
           d[j] = (int32_t)(in[(size_t)lane * 2 * K + K + j] ^ (e & 2));
         }
-        psb_pairmul<K, LB, KARA>(a, b, c, d, n, n0inv, slot);
+        psb_pairmul<K, LB, KARA, KRED>(a, b, c, d, n, dn, n0inv, slot);
       }
     }
 #pragma unroll 1
@@ -152,33 +160,33 @@ __global__ __launch_bounds__(256, MINW) void exp_kernel_bal(const uint32_t* in, 
             c[j] = (int32_t)(in[(size_t)lane * 2 * K + j] ^ (idx & 1));
             d[j] = (int32_t)(in[(size_t)lane * 2 * K + K + j] ^ (idx & 2));
           }
-          psb_pairmul<K, LB, KARA>(a, b, c, d, n, n0inv, slot);
+          psb_pairmul<K, LB, KARA, KRED>(a, b, c, d, n, dn, n0inv, slot);
         }
-        if (i < wl) psb_pairsqr<K, LB, DBL, KARA>(a, b, n, n0inv);
+        if (i < wl) psb_pairsqr<K, LB, DBL, KARA, KRED>(a, b, n, dn, n0inv);
       }
     }
   } else {
 #pragma unroll 1
   for (int e = 0; e < build; ++e) {
-    if (half) psb_pairsqr<K, LB, DBL, KARA>(a, b, n, n0inv);
+    if (half) psb_pairsqr<K, LB, DBL, KARA, KRED>(a, b, n, dn, n0inv);
 #pragma unroll
     for (int j = 0; j < K; ++j) {
       c[j] = (int32_t)(in[(size_t)lane * 2 * K + j] ^ (e & 1));
       d[j] = (int32_t)(in[(size_t)lane * 2 * K + K + j] ^ (e & 2));
     }
-    psb_pairmul<K, LB, KARA>(a, b, c, d, n, n0inv, slot);
+    psb_pairmul<K, LB, KARA, KRED>(a, b, c, d, n, dn, n0inv, slot);
   }
 #pragma unroll 1
   for (int wi = 0; wi < nwin; ++wi) {
 #pragma unroll 1
-    for (int i = 0; i < w; ++i) psb_pairsqr<K, LB, DBL, KARA>(a, b, n, n0inv);
+    for (int i = 0; i < w; ++i) psb_pairsqr<K, LB, DBL, KARA, KRED>(a, b, n, dn, n0inv);
     if (do_mul) {
 #pragma unroll
       for (int j = 0; j < K; ++j) {
         c[j] = (int32_t)(in[(size_t)lane * 2 * K + j] ^ (wi & 1));
         d[j] = (int32_t)(in[(size_t)lane * 2 * K + K + j] ^ (wi & 2));
       }
-      psb_pairmul<K, LB, KARA>(a, b, c, d, n, n0inv, slot);
+      psb_pairmul<K, LB, KARA, KRED>(a, b, c, d, n, dn, n0inv, slot);
     }
   }
   }
@@ -191,7 +199,7 @@ __global__ __launch_bounds__(256, MINW) void exp_kernel_bal(const uint32_t* in, 
   }
 }
 
-template <int K, int LB, bool DBL, bool ODD = false, bool KARA = false>
+template <int K, int LB, bool DBL, bool ODD = false, bool KARA = false, bool KRED = false>
 void run_exp(const char* name, int blocks, unsigned lds, int build, int half, int nwin, int w, int do_mul) {
   const size_t lanes = (size_t)blocks * 256, waves = lanes / 64;
   std::vector<uint32_t> h(lanes * 2 * K), hn(K);
@@ -208,13 +216,13 @@ void run_exp(const char* name, int blocks, unsigned lds, int build, int half, in
   hipMalloc(&din, h.size() * 4); hipMalloc(&dn, hn.size() * 4); hipMalloc(&dout, h.size() * 4); hipMalloc(&dcyc, waves * 8);
   hipMemcpy(din, h.data(), h.size() * 4, hipMemcpyHostToDevice);
   hipMemcpy(dn, hn.data(), hn.size() * 4, hipMemcpyHostToDevice);
-  if (lds) hipFuncSetAttribute((const void*)exp_kernel_bal<K, LB, 1, DBL, ODD, KARA>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+  if (lds) hipFuncSetAttribute((const void*)exp_kernel_bal<K, LB, 1, DBL, ODD, KARA, KRED>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
   hipEvent_t e0, e1;
   hipEventCreate(&e0); hipEventCreate(&e1);
   std::vector<unsigned long long> cyc(waves);
   for (int rep = 0; rep < 4; ++rep) {
     hipEventRecord(e0);
-    hipLaunchKernelGGL((exp_kernel_bal<K, LB, 1, DBL, ODD, KARA>), dim3(blocks), dim3(256), lds, 0, din, dn, dout, dcyc, n0inv, build, half, nwin, w, do_mul);
+    hipLaunchKernelGGL((exp_kernel_bal<K, LB, 1, DBL, ODD, KARA, KRED>), dim3(blocks), dim3(256), lds, 0, din, dn, dout, dcyc, n0inv, build, half, nwin, w, do_mul);
     hipEventRecord(e1);
     hipEventSynchronize(e1);
     float ms = 0;
@@ -225,8 +233,8 @@ void run_exp(const char* name, int blocks, unsigned lds, int build, int half, in
     for (auto v : cyc) mean += (double)v;
     mean /= waves;
     const int sq = ODD ? 1 + (nwin - 1) * w + half : (half ? build : 0) + nwin * w, mul = build + (do_mul ? nwin : 0);
-    if (rep) printf("%-52s doubled=%d karatsuba=%d  %4d squarings + %3d products  wall %7.3f ms | cycles per exponentiation: mean %.5g (min %.5g max %.5g)"
-                    " | clock held %.3f GHz\n", name, (int)DBL, (int)KARA, sq, mul, ms, mean, (double)cyc.front(), (double)cyc.back(),
+    if (rep) printf("%-52s doubled=%d karatsuba=%d folded=%d  %4d squarings + %3d products  wall %7.3f ms | cycles per exponentiation: mean %.5g (min %.5g max %.5g)"
+                    " | clock held %.3f GHz\n", name, (int)DBL, (int)KARA, (int)KRED, sq, mul, ms, mean, (double)cyc.front(), (double)cyc.back(),
                     (double)cyc.back() / (ms * 1e6));
   }
   hipFree(din); hipFree(dn); hipFree(dout); hipFree(dcyc);
@@ -285,6 +293,15 @@ void run(const char* name, int blocks, unsigned lds, int iters, double instr_per
 }
 
 int main(int argc, char** argv) {
+  if (argc > 1 && argv[1][0] == 'r') {   // `ubench_ps r`: the sixth part alone, the parent's form first, between and last
+    printf("# folded reductions: w=6, odd-power table, lone quarter chip (64 WGs, CU claim, MINW=1)\n");
+    run_exp<36, 29, true, true, true, false>("schoolbook reductions (parent)", 64, 84000, 31, 4, 171, 6, 1);
+    run_exp<36, 29, true, true, true, true>("folded reductions of a2*b and a*c", 64, 84000, 31, 4, 171, 6, 1);
+    run_exp<36, 29, true, true, true, false>("schoolbook reductions (parent)", 64, 84000, 31, 4, 171, 6, 1);
+    run_exp<36, 29, true, true, true, true>("folded reductions of a2*b and a*c", 64, 84000, 31, 4, 171, 6, 1);
+    run_exp<36, 29, true, true, true, false>("schoolbook reductions (parent again)", 64, 84000, 31, 4, 171, 6, 1);
+    return 0;
+  }
   // instructions per window (5 squarings + 1 product + the loop's own) of sq_kernel<38,28,*>: tools/asm_stats.py
   const double ipi38 = argc > 1 ? atof(argv[1]) : 5 * 5560.0 + 7700.0;
   const double ipi38w1 = argc > 2 ? atof(argv[2]) : ipi38;
